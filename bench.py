@@ -20,10 +20,16 @@ N > 1: BASELINE config 5 -- N independent 4096^2 problems (seeds 42..42+N-1), on
 scaling; the 4 residual sums are all-reduced over RCCL every residual iteration so every rank sees
 the global stopping criterion.  value = N * K / max-over-ranks(time).
 
+A plain run sets up, warms up, times the K steps and prints the JSON line.  `--full` adds what the headline
+figure does not need, each a run of its own after the timed one: the rate of the bare iteration loop
+(Solver::Iterate, no host wait) as `iterate_only_it_per_s`, the tolerance-class leg (`value_fmad`,
+`roofline_fmad`, `fmad`) and `cpu_baseline`.  `--dump-outputs DIR` writes the iterates the timed loop left
+(x, y, z, w: what prost.solve hands its caller; x and y for c3) as DIR/<name>.npy in the run's precision;
+vectors beyond a 32 MiB budget are sampled in windows at fixed, seeded offsets (dump_windows).
+
 Inputs are resident in HBM before the timed region.  Timed region = K iterations of the loop a caller
 of prost.solve runs (Solver::IterateChecked: the stopping test of solver.cu:141-150 after every observable
-iteration, i.e. the host waits for the residual sums of every residual iteration); the rate of the bare
-iteration loop (Solver::Iterate, no host wait) is reported beside it as `iterate_only_it_per_s`.
+iteration, i.e. the host waits for the residual sums of every residual iteration).
 Before the W warm-up steps an untimed clock-ramp prelude runs 1500 of the same iterations (~90 ms;
 `prelude_iterations`): the part needs tens of milliseconds of load to reach its steady clocks and the
 driver's `--steps 20 --warmup 5` would otherwise measure the ramp.  The JSON line carries
@@ -45,7 +51,7 @@ driver's `--steps 20 --warmup 5` would otherwise measure the ramp.  The JSON lin
                  Runs of <= 40 steps stamp EVERY launch (launches_timed >= 8 at the driver's --steps 20); a
                  stamped launch does not overlap its neighbours, which costs such a run ~4 % of `value`
                  (`iterate_only_it_per_s` is measured without stamps).
-  cpu_baseline : the CPU oracle (port of the reference path) timed on this host's cores on a bounded
+  cpu_baseline : (--full) the CPU oracle (port of the reference path) timed on this host's cores on a bounded
                  sample of the same workload; `reference_build` = the REAL reference's CPU build
                  (oracle/_ref, single-threaded thrust host backend) timed beside the port at 1024^2
 """
@@ -64,6 +70,29 @@ ALG_FLOATS_PER_PIXEL = 11          # primal pass 5 + dual pass 6
 DUAL_PASS_FLOATS = 6
 HBM_PEAK_GBPS = 8000.0
 TRAFFIC_TABLE = os.path.join(ROOT, "profiles", "traffic_table.json")
+DUMP_BYTES = 32 << 20              # --dump-outputs: at most this many bytes in all
+DUMP_WINDOW = 4096                 # a sampled vector is written as windows of this many consecutive entries
+DUMP_SEED = 20241016
+
+
+def dump_windows(lengths, itemsize, budget=DUMP_BYTES, window=DUMP_WINDOW, seed=DUMP_SEED):
+    """{name: vector length} -> {name: None (write the whole vector) or the sorted offsets of the windows to write}.  When the
+    vectors together fit the budget they are written whole; otherwise every vector gets a share of it in proportion to its length,
+    as non-overlapping windows drawn by a fixed seed: the same entries from run to run and from build to build."""
+    import numpy as np
+    total = sum(lengths.values()) * itemsize
+    if total <= budget:
+        return {k: None for k in lengths}
+    out = {}
+    for i, name in enumerate(sorted(lengths)):
+        n = lengths[name]
+        take = (budget * n // total) // window           # budget * n // total: the entries of this vector the budget pays for
+        if take * window >= n:
+            out[name] = None
+            continue
+        rng = np.random.default_rng([seed, i])
+        out[name] = np.sort(rng.choice(n // window, size=max(take, 1), replace=False)) * window
+    return out
 
 
 def traffic_bytes(kernel, size, chunk_cols, dtype="f32", config=None):
@@ -525,11 +554,15 @@ def main():
     ap.add_argument("--stepsize", default=None, choices=["alg1", "alg2", "goldstein", "boyd"], help="pdhg configs: step-size rule (default alg2, the "
                     "example's; boyd with --residual-iter 1 = the reference's DEFAULT backend options, pdhg.m:4-14)")
     ap.add_argument("--residual-iter", type=int, default=None, help="pdhg configs: residual_iter (default 10)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the bare iteration loop (iterate_only_it_per_s), "
+                    "the tolerance-class leg (value_fmad, roofline_fmad) and the CPU baseline (cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the iterates they left as DIR/<name>.npy "
+                    "(float32 / float64 as --dtype; at most 32 MiB in all, larger vectors as a fixed, seeded sample of windows)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
     ap.add_argument("--no-kernel-timing", action="store_true", help="do not record HIP events inside the timed region")
     ap.add_argument("--arithmetic", default="exact", choices=["exact", "fmad"], help="pdhg configs: the arithmetic class of the MAIN leg (`value`); default exact = "
-                    "bit for bit with the CPU oracle.  With the default, c2 / c3 in f32 run a second leg with 'fmad' and report it as value_fmad / roofline_fmad")
-    ap.add_argument("--no-fmad", action="store_true", help="c2, c3 / f32: skip the second leg that runs the same steps with arithmetic='fmad' (value_fmad, roofline_fmad)")
+                    "bit for bit with the CPU oracle.  With the default and --full, c2 / c3 in f32 run a second leg with 'fmad' and report it as value_fmad / roofline_fmad")
+    ap.add_argument("--no-fmad", action="store_true", help="--full, c2, c3 / f32: skip the second leg that runs the same steps with arithmetic='fmad' (value_fmad, roofline_fmad)")
     ap.add_argument("--no-pair", action="store_true", help="one kernel launch per iteration (allow_pair_kernel = false); not the default configuration")
     args = ap.parse_args()
 
@@ -656,9 +689,26 @@ def main():
     every = args.sample_every or (1 if args.steps <= 40 else 4 if args.steps <= 160 else 8)
     units = cfg["units"]
 
-    def run_leg(backend):
+    np_dtype = np.float32 if args.dtype == "f32" else np.float64
+
+    def write_outputs(solver, st, dump_dir):
+        """--dump-outputs: the iterates as the timed loop left them, in the run's precision (dump_windows picks the entries)"""
+        os.makedirs(dump_dir, exist_ok=True)
+        if st is None:            # c3: the state is 8 GB at the full size; x and y are read from the device window by window
+            lengths = {"x": units, "y": 3 * units}
+        else:
+            lengths = {k: len(st[k]) for k in ("x", "y", "z", "w") if k in st}
+        for name, offsets in dump_windows(lengths, itemsize).items():
+            if st is not None:
+                v = st[name] if offsets is None else st[name][(offsets[:, None] + np.arange(DUMP_WINDOW)).reshape(-1)]
+            else:
+                v = solver.read(name, [0], lengths[name]) if offsets is None else solver.read(name, offsets, DUMP_WINDOW)
+            np.save(os.path.join(dump_dir, name + ".npy"), np.asarray(v, dtype=np_dtype).reshape(-1))
+
+    def run_leg(backend, dump_dir=None):
         """tiny warm-up of the code objects, the solver on the real problem, prelude, W warm-up steps, K timed steps (barrier +
-        synchronize on both sides), the bare iteration loop, the state: one measurement of one backend description"""
+        synchronize on both sides), the state (written to `dump_dir` if given), with --full the bare iteration loop: one
+        measurement of one backend description"""
         # code objects are loaded on a kernel's first launch (milliseconds each): run the same kernel instances once on a
         # tiny problem so that a short --warmup does not pay for that inside or right before the timed region
         tiny = prost.Solver(cfg["tiny"](), backend, opts)
@@ -678,38 +728,45 @@ def main():
         barrier()
         elapsed = time.perf_counter() - t0
         info["kernels"] = solver.kernel_times()          # event pairs recorded inside the timed region, evaluated after it
-        # the bare iteration loop (Solver::Iterate: nobody waits for the residual sums), same K, untimed markers off
-        barrier()
-        elapsed_iterate = solver.iterate(args.steps)["ms"] * 1e-3
-        barrier()
-        # the timed region proper: the K iterations between the two stream synchronisations INSIDE the native command
-        # (info["ms"]); `elapsed` additionally holds the Python -> C marshalling of the call on both sides (~35 us, 3 % of a
-        # 20-step run) and is reported as wall_ms_python_side
-        t = torch.tensor([info["ms"] * 1e-3, elapsed_iterate, elapsed], dtype=torch.float64)          # CPU tensor: gloo
-        if dist is not None:
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        # the state as the timed steps left it, before anything else runs on the solver
         if args.config == "c3":
             # the state is 8 GB at the full size: scalars only, finiteness on three 64 Ki-element windows of x and y read from the device
             st = solver.state(vectors=False)
             seg = min(65536, units)
             probes = [np.asarray(solver.read(v, [0, (ln - seg) // 2, ln - seg], seg)) for v, ln in (("x", units), ("y", 3 * units))]
             finite = bool(all(np.isfinite(p).all() for p in probes))
+            if dump_dir:
+                write_outputs(solver, None, dump_dir)
         else:
             st = solver.state()
             finite = bool(np.isfinite(st["x"]).all() and np.isfinite(st["y"]).all())
+            if dump_dir:
+                write_outputs(solver, st, dump_dir)
             st = {k: v for k, v in st.items() if k not in ("x", "y", "z", "w")}
+        elapsed_iterate = 0.0
+        if args.full:
+            # the bare iteration loop (Solver::Iterate: nobody waits for the residual sums), same K, untimed markers off
+            barrier()
+            elapsed_iterate = solver.iterate(args.steps)["ms"] * 1e-3
+            barrier()
+        # the timed region proper: the K iterations between the two stream synchronisations INSIDE the native command
+        # (info["ms"]); `elapsed` additionally holds the Python -> C marshalling of the call on both sides (~35 us, 3 % of a
+        # 20-step run) and is reported as wall_ms_python_side
+        t = torch.tensor([info["ms"] * 1e-3, elapsed_iterate, elapsed], dtype=torch.float64)          # CPU tensor: gloo
+        if dist is not None:
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
         solver.destroy()
         return {"elapsed": float(t[0].item()), "elapsed_iterate": float(t[1].item()), "elapsed_py": float(t[2].item()), "info": info, "st": st,
                 "finite": finite, "prelude_iters": prelude_iters, "prelude_ms": prelude_ms}
 
-    leg = run_leg(backend)
+    leg = run_leg(backend, args.dump_outputs if rank == 0 else None)
     elapsed, elapsed_iterate, elapsed_py, info, st, finite = leg["elapsed"], leg["elapsed_iterate"], leg["elapsed_py"], leg["info"], leg["st"], leg["finite"]
     prelude_iters, prelude_ms = leg["prelude_iters"], leg["prelude_ms"]
     path = st["path"]
     # the tolerance-class leg (headline config, fp32): the same problem, the same loop, `arithmetic="fmad"` (DESIGN.md section 5;
     # iterates within the tolerance of tests/test_gpu_fmad.py of the exact ones).  `value` above stays the exact run.
     leg_fmad = None
-    if args.config in ("c2", "c3") and args.dtype == "f32" and not args.no_fmad and not args.no_pair and args.arithmetic == "exact":
+    if args.full and args.config in ("c2", "c3") and args.dtype == "f32" and not args.no_fmad and not args.no_pair and args.arithmetic == "exact":
         backend_fmad = [backend[0], dict(backend[1])]
         backend_fmad[1]["arithmetic"] = "fmad"
         leg_fmad = run_leg(backend_fmad)
@@ -740,7 +797,6 @@ def main():
                        "stepsize": backend[1].get("stepsize"), "residual_iter": backend[1].get("residual_iter"),
                        "timed_loop": "Solver::IterateChecked = the loop of prost.solve (stopping test after every observable iteration; "
                                      "tolerances 0, so it never fires)"},
-            "iterate_only_it_per_s": world * args.steps / elapsed_iterate,
             "wall_ms_python_side": 1e3 * elapsed_py,     # barrier -> command -> barrier as seen from Python
             "prelude_iterations": prelude_iters,
             "prelude_ms": prelude_ms,
@@ -752,6 +808,8 @@ def main():
             "algorithmic_equiv_roofline_frac": value * bytes_per_iter / 1e9 / (HBM_PEAK_GBPS * world) if bytes_per_iter else None,
             "iterates_finite": finite,
         }
+        if args.full:
+            out["iterate_only_it_per_s"] = world * args.steps / elapsed_iterate
         if rccl_fallback:
             out["value_without_rccl"] = value
             out["error"] = "the native RCCL communicator could not be created; the run used the host-callback transport over gloo and does not count"
@@ -858,7 +916,7 @@ def main():
                            "note": "the same problem and loop with backend.pdhg(..., arithmetic='fmad'): fused multiply-adds and fp32 reciprocal "
                                    "instructions (what nvcc's default -fmad=true makes of the reference's kernels)%s.  `value` is the "
                                    "exact-arithmetic run, bit for bit with the CPU oracle." % (", up to 4 iterations per launch (kernels_fused_iterk.hip)" if args.config == "c2" else "")}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             threads = os.cpu_count() or 1
             if args.config == "c2":
                 out["cpu_baseline"] = cpu_baseline(n, threads, np.float32 if args.dtype == "f32" else np.float64)

@@ -123,11 +123,38 @@ def misc():
     np.savez_compressed(os.path.join(OUT, "misc.npz"), **out)
 
 
+def live():
+    """the reference's answers on the inputs of the live tests of tests/test_oracle_pinning.py (their cases are generated there):
+    digests of the answers those tests compare bit for bit, the values of the Function1DLq answers they compare to a tolerance"""
+    sys.path.insert(0, os.path.dirname(OUT))
+    import test_oracle_pinning as t
+    out, digests = {}, {}
+    for dt in (np.float32, np.float64):
+        for key, args in t.live_elementwise_cases(dt):
+            r = ref.prox_elem(*args)
+            if args[1] == "lq":
+                out[key] = r
+            else:
+                digests[key] = t.answer_digest(r)
+        for step in t.STEPS:
+            for key, prob, b, o, k in t.live_pdhg_cases(dt, step):
+                r = t.ref_pdhg(prob, b, o, k, dt)
+                for v in "xyzw":
+                    digests[key + "_" + v] = t.answer_digest(r[v])
+    key, prob, b, o, k = t.live_solve_dual_case()
+    r = t.ref_pdhg(prob, b, o, k, np.float32)
+    for v in "xyzw":
+        digests[key + "_" + v] = t.answer_digest(r[v])
+    out["digest_keys"] = np.array(sorted(digests), dtype="S")
+    out["digests"] = np.array([digests[k] for k in sorted(digests)], dtype="S64")
+    np.savez_compressed(os.path.join(OUT, "live_reference.npz"), **out)
+
+
 if __name__ == "__main__":
     assert ref.available() or ref.build(), "oracle/_ref is not built and /root/reference is absent"
-    which = sys.argv[1:] or ["elementwise", "pdhg", "pdhg64", "misc"]
+    which = sys.argv[1:] or ["elementwise", "pdhg", "pdhg64", "misc", "live"]
     for name in which:
-        {"elementwise": elementwise, "pdhg": pdhg, "pdhg64": pdhg64, "misc": misc}[name]()
+        {"elementwise": elementwise, "pdhg": pdhg, "pdhg64": pdhg64, "misc": misc, "live": live}[name]()
     for fn in sorted(os.listdir(OUT)):
         if fn.endswith(".npz"):
             print(fn, os.path.getsize(os.path.join(OUT, fn)) // 1024, "KiB")

@@ -7,6 +7,7 @@ compulsory values per pixel / voxel DESIGN.md section 3 states for that launch. 
 import os
 import re
 
+import numpy as np
 import pytest
 
 import bench
@@ -91,3 +92,22 @@ def test_c4_byte_model():
     assert bench.c4_iteration_bytes("admm:fused-op", 10, px) == outer + 10 * (55 * 4 + 7 * 4) * px
     assert bench.c4_iteration_bytes("admm:generic", 10, px) is None
     assert bench.c4_iteration_bytes("admm:pixel-op", 10, px, 8) > bench.c4_iteration_bytes("admm:pixel-op", 10, px, 4)
+
+
+def test_dump_windows_within_the_budget_and_the_same_every_time():
+    """--dump-outputs: vectors that fit the budget are written whole; larger ones as non-overlapping windows at seeded offsets, the
+    same from call to call, every vector in proportion to its length, all of it within DUMP_BYTES"""
+    small = {"x": 64 * 64, "y": 2 * 64 * 64}
+    assert bench.dump_windows(small, 4) == {"x": None, "y": None}
+    n = 4096 * 4096
+    big = {"x": n, "y": 2 * n, "z": 2 * n, "w": n}
+    for itemsize in (4, 8):
+        a, b = bench.dump_windows(big, itemsize), bench.dump_windows(big, itemsize)
+        assert sorted(a) == sorted(big)
+        written = 0
+        for k, offs in a.items():
+            assert offs is not None and np.array_equal(offs, b[k])
+            assert np.all(offs % bench.DUMP_WINDOW == 0) and np.all(np.diff(offs) >= bench.DUMP_WINDOW) and offs[-1] + bench.DUMP_WINDOW <= big[k]
+            written += len(offs) * bench.DUMP_WINDOW * itemsize
+        assert bench.DUMP_BYTES / 2 < written <= bench.DUMP_BYTES
+        assert abs(len(a["y"]) - 2 * len(a["x"])) <= 1 and not np.array_equal(a["x"], a["w"])

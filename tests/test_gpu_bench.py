@@ -1,6 +1,6 @@
 """bench.py as the driver invokes it, for every BASELINE config it measures (c2 headline, c3, c4), at reduced sizes: the ONE JSON
-line with the contract's keys, a `roofline` object whose kernel time was measured with HIP events inside the timed region, a
-`cpu_baseline` object from the oracle, the native path (no fallback) -- so that a schema or plumbing error does not wait for
+line with the contract's keys, a `roofline` object whose kernel time was measured with HIP events inside the timed region, with
+--full a `cpu_baseline` object from the oracle, the native path (no fallback) -- so that a schema or plumbing error does not wait for
 the round-end run.  The bench process is started from the fork server (a process that has touched the GPU must not spawn)."""
 import json
 import multiprocessing as mp
@@ -52,7 +52,7 @@ def _check_contract(d, steps, warmup, dtype="f32"):
 
 
 def test_bench_c2_reduced():
-    d = _bench("--steps", "20", "--warmup", "5", "--size", "512", "--prelude-iters", "50")
+    d = _bench("--steps", "20", "--warmup", "5", "--size", "512", "--prelude-iters", "50", "--full")
     _check_contract(d, 20, 5)
     assert d["config"]["name"] == "c2" and d["config"]["path"] == "pdhg:fused-grad2d" and d["metric"] == "PDHG iters/sec, ROF-TV 512^2 fp32"
     assert d["roofline"]["kernel"].startswith("fused_iter2d") and d["roofline"]["algorithmic_bytes_per_launch"] in (11 * 4 * 512 * 512, 22 * 4 * 512 * 512)
@@ -65,10 +65,41 @@ def test_bench_c2_reduced():
     assert any(k.endswith("+residuals") for k in rf["all_kernels"]) and "two_pass_equiv_GBps" in d and "achieved_hbm_GBps" not in d
 
 
+def test_bench_plain_run_and_its_dumped_outputs(tmp_path):
+    """a plain run (no --full) measures the headline alone: no bare-loop rate, no tolerance-class leg, no CPU baseline.  With
+    --dump-outputs it writes x, y, z, w as the timed loop left them, fp32 -- bit for bit the CPU oracle's iterates after the same
+    prelude + warm-up + timed iterations (exact class)"""
+    import numpy as np
+
+    import oracle
+    import prost_amd as prost
+    from prost_amd import synthetic
+    out = tmp_path / "outputs"
+    d = _bench("--steps", "20", "--warmup", "5", "--size", "64", "--prelude-iters", "10", "--dump-outputs", str(out))
+    for k in CONTRACT_KEYS[:-1]:
+        assert k in d, k
+    assert d["steps"] == 20 and d["warmup"] == 5 and d["dtype"] == "f32" and d["higher_is_better"] is True and d["iterates_finite"]
+    assert d["value"] > 0 and abs(d["value"] - 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"] and d["config"]["path"] == "pdhg:fused-grad2d"
+    for k in ("cpu_baseline", "value_fmad", "roofline_fmad", "fmad", "iterate_only_it_per_s"):
+        assert k not in d, k
+    prob = synthetic.rof_problem(64, 64, lmb=10.0, seed=42)[0]
+    prob.finalize()
+    b = prost.backend.pdhg(stepsize="alg2", residual_iter=10, alg2_gamma=0.5)
+    o = prost.options(max_iters=10 ** 9, num_cback_calls=0, verbose=False, tol_rel_primal=0, tol_rel_dual=0, tol_abs_primal=0, tol_abs_dual=0)
+    orc = oracle.Solver(prob.data, prob.nrows, prob.ncols, b, o, np.float32)
+    orc.initialize()
+    orc.iterate(10 + 5 + 20)
+    ost = orc.state()
+    assert sorted(os.listdir(out)) == ["w.npy", "x.npy", "y.npy", "z.npy"]
+    for v in "xyzw":
+        got = np.load(out / (v + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, np.asarray(ost[v], dtype=np.float32)), v
+
+
 def test_bench_c2_reduced_fp64_and_the_reference_default_options():
     """--dtype f64 (the precision the reference front end ships with, config.hpp:7) and --stepsize boyd --residual-iter 1 (the
     reference's DEFAULT backend options, pdhg.m:4-14) keep the schema"""
-    d = _bench("--steps", "20", "--warmup", "5", "--size", "512", "--prelude-iters", "50", "--dtype", "f64")
+    d = _bench("--steps", "20", "--warmup", "5", "--size", "512", "--prelude-iters", "50", "--dtype", "f64", "--full")
     _check_contract(d, 20, 5, "f64")
     assert d["metric"] == "PDHG iters/sec, ROF-TV 512^2 fp64" and d["roofline"]["compulsory_bytes_per_launch"] == 7 * 8 * 512 * 512
     d = _bench("--steps", "40", "--warmup", "5", "--size", "512", "--prelude-iters", "50", "--stepsize", "boyd", "--residual-iter", "1", "--no-cpu-baseline")
@@ -77,7 +108,7 @@ def test_bench_c2_reduced_fp64_and_the_reference_default_options():
 
 
 def test_bench_c3_reduced():
-    d = _bench("--config", "c3", "--steps", "20", "--warmup", "5", "--volume", "96", "64", "8", "--prelude-iters", "20")
+    d = _bench("--config", "c3", "--steps", "20", "--warmup", "5", "--volume", "96", "64", "8", "--prelude-iters", "20", "--full")
     _check_contract(d, 20, 5)
     assert d["config"]["name"] == "c3" and d["config"]["path"] == "pdhg:fused-grad3d" and d["metric"] == "PDHG iters/sec, TV-3D 96x64x8 fp32"
     vox = 96 * 64 * 8
@@ -94,7 +125,7 @@ def bench_module():
 
 
 def test_bench_c4_reduced():
-    d = _bench("--config", "c4", "--steps", "20", "--warmup", "5", "--size", "128", "--prelude-iters", "10")
+    d = _bench("--config", "c4", "--steps", "20", "--warmup", "5", "--size", "128", "--prelude-iters", "10", "--full")
     _check_contract(d, 20, 5)
     assert d["config"]["name"] == "c4" and d["config"]["path"] == "admm:pixel-op" and d["metric"] == "ADMM iters/sec, TV-L1 flow-like 128^2 fp32"
     r = d["roofline"]
@@ -108,7 +139,7 @@ def test_bench_c4_reduced():
 
 def test_bench_c4w_reduced():
     """BASELINE.json configs[3] as worded (warp matrix): the two-launch CG rounds with the rows of W gathered (round 6; four launches before)"""
-    d = _bench("--config", "c4w", "--steps", "20", "--warmup", "5", "--size", "128", "--prelude-iters", "10")
+    d = _bench("--config", "c4w", "--steps", "20", "--warmup", "5", "--size", "128", "--prelude-iters", "10", "--full")
     _check_contract(d, 20, 5)
     assert d["config"]["name"] == "c4w" and d["config"]["path"] == "admm:pixel-op" and "warp matrix" in d["config"]["workload"]
     r = d["roofline"]

@@ -2,11 +2,14 @@
 
  * golden fixtures under tests/golden/ were produced by the REAL reference code (oracle/_ref,
    compiled from /root/reference where it lies; generator: tests/golden/make_golden.py);
- * when oracle/_ref/libprost_ref.so is present (build container, or shipped to the GPU box) the
-   oracle is additionally compared live on fresh random inputs.
+ * the "live" tests compare the oracle on fresh random inputs from fixed seeds with the reference's answers on them,
+   stored in tests/golden/live_reference.npz (digests of the answers compared bit for bit); where
+   oracle/_ref/libprost_ref.so is present they are computed afresh as well and must match the stored ones.
 Bar: bit-exact, except Function1DLq whose Newton/pow path depends on the libm pow overload the
 host compiler picks for the reference's unqualified pow() (documented in DESIGN.md).
 """
+import functools
+import hashlib
 import os
 
 import numpy as np
@@ -125,12 +128,40 @@ def test_misc_golden():
         assert np.allclose(got[dimx * count:], g["epi_y_" + name], rtol=tol, atol=tol)
 
 
-needs_ref = pytest.mark.skipif(not ref.available(), reason="oracle/_ref not built (needs /root/reference)")
+# The reference's answers on the inputs of the live tests below, stored by tests/golden/make_golden.py (live) where oracle/_ref was
+# built: the answers compared bit for bit as digests (answer_digest), the Function1DLq answers (compared to a tolerance) as values.
+# Where oracle/_ref is built here as well, the reference's live answers must match the same records.
+LIVE = os.path.join(GOLD, "live_reference.npz")
 
 
-@needs_ref
-@pytest.mark.parametrize("dtype", DTYPES)
-def test_live_elementwise_vs_reference(dtype):
+@functools.lru_cache(maxsize=None)
+def _live():
+    g = dict(np.load(LIVE))
+    g.update(zip((k.decode() for k in g.pop("digest_keys")), (d.decode() for d in g.pop("digests"))))
+    return g
+
+
+def answer_digest(a):
+    """SHA-256 of an answer's shape and values as float64, -0 as +0 and every NaN as one NaN: two answers have the same digest
+    exactly when np.array_equal(a, b, equal_nan=True)"""
+    a = np.asarray(a, dtype=np.float64) + 0.0
+    a[np.isnan(a)] = np.nan
+    return hashlib.sha256(repr(a.shape).encode() + a.tobytes()).hexdigest()
+
+
+def check_reference(key, got, compute, close=None):
+    """`got` (the oracle's answer) against the reference's answer on the same inputs: its stored values compared with `close` when
+    given, else its stored digest; the reference's live answer (`compute()`) must match the same record where oracle/_ref is built"""
+    exp = _live()[key]
+    for name, a in [("oracle", got)] + ([("live reference", compute())] if ref.available() else []):
+        if close is not None:
+            assert close(a, exp), (name, key)
+        else:
+            assert answer_digest(a) == exp, (name, key)
+
+
+def live_elementwise_cases(dtype):
+    """-> (key, prox_elem arguments) of test_live_elementwise_vs_reference: fresh random inputs from a fixed seed"""
     rng = np.random.default_rng(11)
     count = 301
     for op in (0, 1):
@@ -142,19 +173,12 @@ def test_live_elementwise_vs_reference(dtype):
                     td = rng.uniform(0.05, 3, count * dim).astype(dtype)
                     coeffs = [rng.uniform(0.2, 3, count), rng.uniform(-2, 2, count), rng.uniform(0.1, 3, count),
                               rng.uniform(-1, 1, count), rng.uniform(0, 2, count), 0.5 if fn == "lq" else 0.9, 0.6]
-                    a = oracle.prox_elem(op, fn, arg, td, 1.7, count, dim, il, coeffs, inv)
-                    b = ref.prox_elem(op, fn, arg, td, 1.7, count, dim, il, coeffs, inv)
-                    if fn == "lq":
-                        assert close_lq(a, b, dtype)
-                    else:
-                        assert np.array_equal(a, b, equal_nan=True), (fn, op, il, inv)
+                    key = "elem_%s_op%d_%s_il%d_inv%d" % (np.dtype(dtype).name, op, fn, il, inv)
+                    yield key, (op, fn, arg, td, 1.7, count, dim, il, coeffs, inv)
 
 
-@needs_ref
-@pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("step", STEPS)
-def test_live_pdhg_vs_reference_backend(dtype, step):
-    """reference BackendPDHG + Problem + LinearOperator + ProxMoreau, leaf kernels via plugins"""
+def live_pdhg_cases(dtype, step):
+    """-> (key, problem, backend, options, iterations) of test_live_pdhg_vs_reference_backend"""
     for shape, moreau in (((24, 20, 1), False), ((9, 14, 3), True)):
         nx, ny, L = shape
         prob, u, q, f = synthetic.rof_problem(nx, ny, L, seed=3)
@@ -164,22 +188,47 @@ def test_live_pdhg_vs_reference_backend(dtype, step):
         b = prost.backend.pdhg(stepsize=step, residual_iter=4, alg2_gamma=0.3)
         x0 = np.linspace(0, 1, prob.ncols); y0 = np.linspace(-0.5, 0.5, prob.nrows)
         o = prost.options(max_iters=30, num_cback_calls=0, verbose=False, x0=x0, y0=y0)
-        s = oracle.Solver(prob.data, prob.nrows, prob.ncols, b, o, dtype)
-        s.initialize(); s.iterate(30)
-        st = s.state()
-        r = ref.RefProblem(prob.data, prob.nrows, prob.ncols, dtype).pdhg(b[1], o, 30)
-        for v in "xyzw":
-            assert np.array_equal(st[v], r[v]), (shape, v, np.abs(st[v] - r[v]).max())
+        yield "pdhg_%s_%s_%dx%dx%d" % (np.dtype(dtype).name, step, nx, ny, L), prob, b, o, 30
 
 
-@needs_ref
-def test_live_solve_dual_vs_reference():
+def live_solve_dual_case():
+    """-> (key, problem, backend, options, iterations) of test_live_solve_dual_vs_reference"""
     prob, u, q, f = synthetic.rof_problem(12, 10, 1, seed=4)
     b = prost.backend.pdhg(stepsize="alg1", residual_iter=2)
     o = prost.options(max_iters=20, num_cback_calls=0, verbose=False, solve_dual=True)
+    return "solve_dual_float32", prob, b, o, 20
+
+
+def ref_pdhg(prob, b, o, k, dtype):
+    return ref.RefProblem(prob.data, prob.nrows, prob.ncols, dtype).pdhg(b[1], o, k)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_live_elementwise_vs_reference(dtype):
+    for key, args in live_elementwise_cases(dtype):
+        fn = args[1]
+        a = oracle.prox_elem(*args)
+        check_reference(key, a, lambda: ref.prox_elem(*args), (lambda x, y: close_lq(x, y, dtype)) if fn == "lq" else None)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("step", STEPS)
+def test_live_pdhg_vs_reference_backend(dtype, step):
+    """reference BackendPDHG + Problem + LinearOperator + ProxMoreau, leaf kernels via plugins"""
+    for key, prob, b, o, k in live_pdhg_cases(dtype, step):
+        s = oracle.Solver(prob.data, prob.nrows, prob.ncols, b, o, dtype)
+        s.initialize(); s.iterate(k)
+        st = s.state()
+        live = functools.lru_cache(maxsize=None)(lambda: ref_pdhg(prob, b, o, k, dtype))
+        for v in "xyzw":
+            check_reference(key + "_" + v, st[v], lambda: live()[v])
+
+
+def test_live_solve_dual_vs_reference():
+    key, prob, b, o, k = live_solve_dual_case()
     s = oracle.Solver(prob.data, prob.nrows, prob.ncols, b, o, np.float32)
-    s.initialize(); s.iterate(20)
+    s.initialize(); s.iterate(k)
     st = s.state()
-    r = ref.RefProblem(prob.data, prob.nrows, prob.ncols, np.float32).pdhg(b[1], o, 20)
+    live = functools.lru_cache(maxsize=None)(lambda: ref_pdhg(prob, b, o, k, np.float32))
     for v in "xyzw":
-        assert np.array_equal(st[v], r[v]), v
+        check_reference(key + "_" + v, st[v], lambda: live()[v])

@@ -2,38 +2,38 @@
 # On the GPU box: everything profiles/r04_* and DESIGN.md section 6 quote for round 4.  usage: bash tools/collect_r04.sh   (outputs under gpurun_out/r04c/)
 R=$PWD; O=$R/gpurun_out/r04c; mkdir -p $O
 # ---- C2 (headline): the driver's invocation, the default run, fp64
-python3 bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_driver_invocation.json
-python3 bench.py 2>/dev/null | tail -1 > $O/bench.json
-python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_driver_invocation_2.json
-python3 bench.py --dtype f64 2>/dev/null | tail -1 > $O/bench_f64.json
-python3 bench.py --dtype f64 --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_f64_driver_invocation.json
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_driver_invocation.json
+python3 bench.py --full 2>/dev/null | tail -1 > $O/bench.json
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_driver_invocation_2.json
+python3 bench.py --full --dtype f64 2>/dev/null | tail -1 > $O/bench_f64.json
+python3 bench.py --full --dtype f64 --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_f64_driver_invocation.json
 # ---- the reference's DEFAULT backend options (pdhg.m:4-14: boyd, residual_iter = 1): rule on the device / on the host
 for dev in 1 0; do
   for size in 4096 1024 256; do
-    PROST_BENCH_DEVICE_RULES=$dev python3 bench.py --stepsize boyd --residual-iter 1 --size $size --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_boyd_r1_${size}_dev$dev.json
+    PROST_BENCH_DEVICE_RULES=$dev python3 bench.py --full --stepsize boyd --residual-iter 1 --size $size --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_boyd_r1_${size}_dev$dev.json
   done
-  PROST_BENCH_DEVICE_RULES=$dev python3 bench.py --stepsize boyd --residual-iter 10 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_boyd_r10_4096_dev$dev.json
+  PROST_BENCH_DEVICE_RULES=$dev python3 bench.py --full --stepsize boyd --residual-iter 10 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_boyd_r10_4096_dev$dev.json
 done
 # ---- C3 / C4
-python3 bench.py --config c3 2>/dev/null | tail -1 > $O/bench_c3.json
-python3 bench.py --config c4 2>/dev/null | tail -1 > $O/bench_c4.json
+python3 bench.py --full --config c3 2>/dev/null | tail -1 > $O/bench_c3.json
+python3 bench.py --full --config c4 2>/dev/null | tail -1 > $O/bench_c4.json
 # ---- rocprofv3 kernel stats of the same commands
 cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats -- python3 $R/bench.py --no-cpu-baseline > $O/bench_under_rocprof.json 2>/dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats_short -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_short_under_rocprof.json 2>/dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats_f64 -- python3 $R/bench.py --dtype f64 --no-cpu-baseline > $O/bench_f64_under_rocprof.json 2>/dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats_boyd_r1 -- python3 $R/bench.py --stepsize boyd --residual-iter 1 --no-cpu-baseline > $O/bench_boyd_r1_under_rocprof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats -- python3 $R/bench.py --full --no-cpu-baseline > $O/bench_under_rocprof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats_short -- python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_short_under_rocprof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats_f64 -- python3 $R/bench.py --full --dtype f64 --no-cpu-baseline > $O/bench_f64_under_rocprof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats_boyd_r1 -- python3 $R/bench.py --full --stepsize boyd --residual-iter 1 --no-cpu-baseline > $O/bench_boyd_r1_under_rocprof.json 2>/dev/null
 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats_sparse -- python3 $R/tools/sparse_rof_rate.py 2048 2000 1 > $O/sparse_rof_under_rocprof.txt 2>/dev/null
 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats_sparse_generic -- python3 $R/tools/sparse_rof_rate.py 2048 600 0 > $O/sparse_rof_generic_under_rocprof.txt 2>/dev/null
 # ---- HBM traffic (separate --pmc passes): fp32 and fp64 pair kernels, the position-dependent instance
 for dt in f32 f64; do
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O -o pmc_fetch_$dt -- python3 $R/bench.py --dtype $dt --steps 60 --warmup 10 --prelude-iters 0 --no-cpu-baseline > /dev/null 2>&1
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O -o pmc_write_$dt -- python3 $R/bench.py --dtype $dt --steps 60 --warmup 10 --prelude-iters 0 --no-cpu-baseline > /dev/null 2>&1
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O -o pmc_fetch_$dt -- python3 $R/bench.py --full --dtype $dt --steps 60 --warmup 10 --prelude-iters 0 --no-cpu-baseline > /dev/null 2>&1
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O -o pmc_write_$dt -- python3 $R/bench.py --full --dtype $dt --steps 60 --warmup 10 --prelude-iters 0 --no-cpu-baseline > /dev/null 2>&1
 done
 # C3: kernel stats, traffic and the instruction mix of the 3-D pair kernel
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats_c3 -- python3 $R/bench.py --config c3 --no-cpu-baseline > $O/bench_c3_under_rocprof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats_c3 -- python3 $R/bench.py --full --config c3 --no-cpu-baseline > $O/bench_c3_under_rocprof.json 2>/dev/null
 for c in FETCH_SIZE WRITE_SIZE SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_BRANCH; do
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O -o pmc_c3_$c -- python3 $R/bench.py --config c3 --steps 40 --warmup 10 --prelude-iters 0 --no-cpu-baseline > /dev/null 2>&1
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O -o pmc_c3_$c -- python3 $R/bench.py --full --config c3 --steps 40 --warmup 10 --prelude-iters 0 --no-cpu-baseline > /dev/null 2>&1
 done
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O -o pmc_fetch_sparse -- python3 $R/tools/sparse_rof_rate.py 4096 60 1 > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O -o pmc_write_sparse -- python3 $R/tools/sparse_rof_rate.py 4096 60 1 > /dev/null 2>&1

@@ -3,26 +3,26 @@
 R=$PWD; O=$R/gpurun_out/r05c; mkdir -p $O
 ( nproc; cat /sys/fs/cgroup/cpu.max 2>/dev/null; lscpu | grep -E "Model name|Socket|NUMA|Thread|Core|^CPU\(s\)" ) > $O/host_info.txt 2>&1
 # ---- C2 (headline): the driver's invocation, the default run, fp64
-python3 bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_driver_invocation.json
-python3 bench.py 2>/dev/null | tail -1 > $O/bench.json
-python3 bench.py --dtype f64 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_f64.json
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_driver_invocation.json
+python3 bench.py --full 2>/dev/null | tail -1 > $O/bench.json
+python3 bench.py --full --dtype f64 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_f64.json
 # ---- the reference's DEFAULT backend options (pdhg.m:4-14: boyd, residual_iter = 1)
 for size in 4096 1024 256; do
-  python3 bench.py --stepsize boyd --residual-iter 1 --size $size --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_boyd_r1_${size}.json
+  python3 bench.py --full --stepsize boyd --residual-iter 1 --size $size --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_boyd_r1_${size}.json
 done
 # ---- C3 / C4 (+ C3 with the default options: rule on the device / on the host)
-python3 bench.py --config c3 2>/dev/null | tail -1 > $O/bench_c3.json
-for dev in 1 0; do PROST_BENCH_DEVICE_RULES=$dev python3 bench.py --config c3 --stepsize boyd --residual-iter 1 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_c3_boyd_r1_dev$dev.json; done
-python3 bench.py --config c4 2>/dev/null | tail -1 > $O/bench_c4.json
-python3 bench.py --config c4 --dtype f64 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_c4_f64.json
+python3 bench.py --full --config c3 2>/dev/null | tail -1 > $O/bench_c3.json
+for dev in 1 0; do PROST_BENCH_DEVICE_RULES=$dev python3 bench.py --full --config c3 --stepsize boyd --residual-iter 1 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_c3_boyd_r1_dev$dev.json; done
+python3 bench.py --full --config c4 2>/dev/null | tail -1 > $O/bench_c4.json
+python3 bench.py --full --config c4 --dtype f64 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_c4_f64.json
 # ---- rocprofv3 kernel stats of the same commands
 cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats -- python3 $R/bench.py --no-cpu-baseline > $O/bench_under_rocprof.json 2>/dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats_c3 -- python3 $R/bench.py --config c3 --no-cpu-baseline > $O/bench_c3_under_rocprof.json 2>/dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats_c4 -- python3 $R/bench.py --config c4 --no-cpu-baseline > $O/bench_c4_under_rocprof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats -- python3 $R/bench.py --full --no-cpu-baseline > $O/bench_under_rocprof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats_c3 -- python3 $R/bench.py --full --config c3 --no-cpu-baseline > $O/bench_c3_under_rocprof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats_c4 -- python3 $R/bench.py --full --config c4 --no-cpu-baseline > $O/bench_c4_under_rocprof.json 2>/dev/null
 # ---- HBM traffic of the C4 round kernels (separate --pmc passes)
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O -o pmc_c4_$c -- python3 $R/bench.py --config c4 --steps 60 --warmup 10 --prelude-iters 0 --no-cpu-baseline > /dev/null 2>&1
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O -o pmc_c4_$c -- python3 $R/bench.py --full --config c4 --steps 60 --warmup 10 --prelude-iters 0 --no-cpu-baseline > /dev/null 2>&1
 done
 cd $R
 python3 - <<PY > $O/pmc_summary.txt

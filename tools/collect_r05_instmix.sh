@@ -19,7 +19,7 @@ run_cfg() {   # tag, bench args...
   for grp in "$G1" "$G2" "$G3" "$G4" "$G5"; do
     i=$((i+1))
     [ -z "$grp" ] && continue
-    rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $O/$tag -o p$i -- python3 $R/bench.py "$@" --no-cpu-baseline --prelude-iters 0 > $O/${tag}_p$i.log 2>&1
+    rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $O/$tag -o p$i -- python3 $R/bench.py --full "$@" --no-cpu-baseline --prelude-iters 0 > $O/${tag}_p$i.log 2>&1
   done
   python3 - "$O/$tag" > $O/instmix_$tag.txt <<'PY'
 import collections, csv, glob, sys

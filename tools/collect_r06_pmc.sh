@@ -9,7 +9,7 @@ run() {   # tag, bench args...
   local tag=$1; shift
   for c in FETCH_SIZE WRITE_SIZE; do
     rm -rf /tmp/pmc_${tag}_$c
-    rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmc_${tag}_$c -o p -- python3 $R/bench.py "$@" --no-cpu-baseline --no-kernel-timing --prelude-iters 0 > /dev/null 2>&1
+    rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmc_${tag}_$c -o p -- python3 $R/bench.py --full "$@" --no-cpu-baseline --no-kernel-timing --prelude-iters 0 > /dev/null 2>&1
   done
   python3 - $tag "$*" <<'PY'
 import csv, glob, collections, sys

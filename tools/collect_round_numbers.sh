@@ -12,6 +12,6 @@ run env QUICK=1 python tools/microbench_iter2.py 4096 0,0 f64
 run env QUICK=1 python tools/microbench_iter2.py 4096 0,0 f32 abs
 run python tools/microbench_iter2.py 4096 0 f32
 run python tools/microbench_iter_mc.py 4096 3
-run python bench.py --no-pair --no-cpu-baseline
-run env PROST_ITER2_NO_RING=1 python bench.py --no-cpu-baseline
+run python bench.py --full --no-pair --no-cpu-baseline
+run env PROST_ITER2_NO_RING=1 python bench.py --full --no-cpu-baseline
 grep -v "^$" $O | cut -c1-400

@@ -4,7 +4,7 @@ R=$PWD
 cd /tmp; export TMPDIR=/tmp
 for grp in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmc_c4_$grp
-  rocprofv3 --pmc $grp --kernel-trace --output-format csv -d /tmp/pmc_c4_$grp -o p -- python3 $R/bench.py --config c4 --steps 30 --warmup 5 --prelude-iters 0 --no-cpu-baseline --no-kernel-timing > /dev/null 2>&1
+  rocprofv3 --pmc $grp --kernel-trace --output-format csv -d /tmp/pmc_c4_$grp -o p -- python3 $R/bench.py --full --config c4 --steps 30 --warmup 5 --prelude-iters 0 --no-cpu-baseline --no-kernel-timing > /dev/null 2>&1
 done
 python3 - <<'PY'
 import csv, glob, collections
