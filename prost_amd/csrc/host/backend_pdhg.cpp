@@ -247,33 +247,34 @@ void BackendPDHG<T>::Initialize() {
     CheckHip(prost_hip_malloc(&op_workspace_, 2 * (size_t)kOpSumSlots * 4 * sizeof(double)), "malloc");
     CheckHip(prost_hip_memset(op_workspace_, 0, 2 * (size_t)kOpSumSlots * 4 * sizeof(double), CurrentStream()), "memset");
   }
-  single_kernel_ = fused_ && opts_.allow_single_kernel && prost_hip_fused_iteration_supported(&desc_, dtype_id<T>()) == 1;
-  single3d_ = fused_ && !single_kernel_ && opts_.allow_single_kernel && prost_hip_fused_iteration3d_supported(&desc_, dtype_id<T>()) == 1;
-  single3d_pw_ = single3d_ && prost_hip_fused_iteration3d_pw_supported(&desc_, dtype_id<T>()) == 1;
-  single_mc_ = fused_ && !single_kernel_ && !single3d_ && opts_.allow_single_kernel && prost_hip_fused_iteration_mc_supported(&desc_, dtype_id<T>()) == 1;
+  const bool single_kernel = fused_ && opts_.allow_single_kernel && prost_hip_fused_iteration_supported(&desc_, dtype_id<T>()) == 1;
+  const bool single3d = fused_ && !single_kernel && opts_.allow_single_kernel && prost_hip_fused_iteration3d_supported(&desc_, dtype_id<T>()) == 1;
+  single_pw_ = single3d && prost_hip_fused_iteration3d_pw_supported(&desc_, dtype_id<T>()) == 1;
+  const bool single_mc = fused_ && !single_kernel && !single3d && opts_.allow_single_kernel && prost_hip_fused_iteration_mc_supported(&desc_, dtype_id<T>()) == 1;
+  single_ = single_kernel ? kSingleGray : single3d ? kSingleVol : single_mc ? kSingleMc : kTwoPass;
 
   x_.resize(n); x_prev_.resize(n); y_.resize(m); y_prev_.resize(m);
   if (!fused_) { kty_prev_.resize(n); kty_.resize(n); kx_.resize(m); kx_prev_.resize(m); temp_.resize(l); }
   TryMaskedPairShape();
-  pair_kernel_ = single_kernel_ && opts_.allow_pair_kernel && prost_hip_fused_iteration2_profitable(&desc_pair_, dtype_id<T>()) == 1;
+  const bool pair_kernel = single_kernel && opts_.allow_pair_kernel && prost_hip_fused_iteration2_profitable(&desc_pair_, dtype_id<T>()) == 1;
   // (volumes of fewer than 4 planes leave 13 of the 16 wavefronts of a workgroup idle: 2048^2 x 2 runs 0.125 ms per iteration in pairs,
   // 0.086 ms in single launches; from 4 planes on the pairs win, 0.127 against 0.206 ms)
-  pair3d_ = fused_ && desc_.is3d && desc_.L >= 4 && opts_.allow_single_kernel && opts_.allow_pair_kernel && prost_hip_fused_iteration3d_x2_supported(&desc_, dtype_id<T>()) == 1;
+  const bool pair3d = fused_ && desc_.is3d && desc_.L >= 4 && opts_.allow_single_kernel && opts_.allow_pair_kernel && prost_hip_fused_iteration3d_x2_supported(&desc_, dtype_id<T>()) == 1;
   // 2-4 channels: the channels on the wavefronts of a workgroup, two iterations per launch
   // (also at heights the single-iteration kernels do not take: the other iterations then run the two passes)
-  // (L = 2 at heights the gray-value pair kernel takes: PerformIterations launches that one, so only one of the two flags is set --
+  // (L = 2 at heights the gray-value pair kernel takes: PerformIterations launches that one, so only one of the two is chosen --
   // the kernel names and chunk lengths KernelTimes reports then belong to the kernel that ran)
-  pair_mc_ = fused_ && !pair_kernel_ && !desc_.is3d && desc_.L >= 2 && desc_.L <= 4 && opts_.allow_single_kernel && opts_.allow_pair_kernel &&
+  const bool pair_mc = fused_ && !pair_kernel && !desc_.is3d && desc_.L >= 2 && desc_.L <= 4 && opts_.allow_single_kernel && opts_.allow_pair_kernel &&
              prost_hip_fused_iteration_mc_x2_profitable(&desc_pair_, dtype_id<T>()) == 1;
-  // third buffers: where every residual iteration (single-kernel paths) or every other pair (pair_kernel_: stored intermediate
+  // third buffers: where every residual iteration (single-kernel paths) or every other pair (gray-value pairs: stored intermediate
   // iterate) uses them they are allocated here; the 3-D / multi-channel pair paths without them need a third buffer only to
   // rebuild the previous iterate (RebuildPrevious: read-out, callbacks) and allocate it there -- 4 n + 4 m values less resident
   // at the 2048 x 2048 x 64 size until somebody reads the solution
   // tolerance-class arithmetic (Options::arithmetic): where the K-iterations-per-launch kernel takes the description, groups of up to
   // kGroupMax iterations replace the pairs; elsewhere the solve stays exact (exact results satisfy every tolerance)
-  group_max_ = 0; stale_group_ = false; stale_count_ = 2;
+  group_max_ = 0; last_ = LaunchSteps();
   desc_.arith = desc_pair_.arith = PROST_HIP_ARITH_EXACT;
-  if (pair_kernel_ && owned_x1_ == 0 && opts_.group_max != 1) {
+  if (pair_kernel && owned_x1_ == 0 && opts_.group_max != 1) {
     prost_hip_fused_desc probe = desc_pair_;
     probe.arith = opts_.arithmetic == PROST_HIP_ARITH_FMAD ? PROST_HIP_ARITH_FMAD : PROST_HIP_ARITH_EXACT;
     const int kmax = prost_hip_fused_iterationk_max(&probe, dtype_id<T>());
@@ -284,18 +285,19 @@ void BackendPDHG<T>::Initialize() {
     if (kmax >= 2 && want >= 2) { group_max_ = std::min(std::min(kmax, kGroupMax), want); desc_pair_.arith = probe.arith; }
   }
   // gradient3d volumes / 2-4 channels: the pair kernels have tolerance-class instances of their own (two iterations per launch as before)
-  if (opts_.arithmetic == PROST_HIP_ARITH_FMAD && pair3d_) {
+  if (opts_.arithmetic == PROST_HIP_ARITH_FMAD && pair3d) {
     prost_hip_fused_desc probe = desc_;
     probe.arith = PROST_HIP_ARITH_FMAD;
     if (prost_hip_fused_iteration3d_x2_arith(&probe, dtype_id<T>()) == PROST_HIP_ARITH_FMAD) desc_.arith = PROST_HIP_ARITH_FMAD;
   }
-  if (opts_.arithmetic == PROST_HIP_ARITH_FMAD && pair_mc_) {
+  if (opts_.arithmetic == PROST_HIP_ARITH_FMAD && pair_mc) {
     prost_hip_fused_desc probe = desc_pair_;
     probe.arith = PROST_HIP_ARITH_FMAD;
     if (prost_hip_fused_iteration_mc_x2_arith(&probe, dtype_id<T>()) == PROST_HIP_ARITH_FMAD) desc_pair_.arith = PROST_HIP_ARITH_FMAD;
   }
-  if (pair_kernel_) x_spare_.resize(n);
-  if (single_kernel_ || single3d_ || single_mc_) y_spare_.resize(m);
+  multi_ = pair_kernel ? (group_max_ >= 2 ? kMultiGroup : kMultiPair) : pair3d ? kMultiVol : pair_mc ? kMultiMc : kMultiNone;
+  if (pair_kernel) x_spare_.resize(n);
+  if (single_ != kTwoPass) y_spare_.resize(m);
 
   CheckHip(prost_hip_malloc((void**)&res_dev_, 4 * sizeof(double)), "malloc");
   CheckHip(prost_hip_memset(res_dev_, 0, 4 * sizeof(double), CurrentStream()), "memset");
@@ -318,7 +320,7 @@ void BackendPDHG<T>::Initialize() {
   // reads the record -- prost_hip_fused_iteration_rec, _iteration_mc_rec, _iteration2_rec, _iteration_mc_x2_rec)
   // (round 5: gradient3d as well -- prost_hip_fused_iteration3d_rec, _3d_pw_rec, _3d_x2_rec: the reference's default options on a
   // volume cost a host round trip per iteration before)
-  const bool rec_kernels = single_kernel_ || single_mc_ || single3d_;
+  const bool rec_kernels = single_ != kTwoPass;
   // (column-sharded slabs exchange halos between iterations: on the RCCL transport the exchange is device-side work on the solver's
   // stream, enqueued by the exchange hook inside the batch; on the host-callback transport it needs the host and the host loop stays)
   const bool slab_ok = owned_x1_ == 0 || (this->comm_ && prost_hip_comm_is_host(this->comm_) == 0);
@@ -393,14 +395,9 @@ void BackendPDHG<T>::PerformIteration() {
   if (fused_) IterationFused(residual_iteration); else IterationGeneric(residual_iteration);
 }
 
-/// Two iterations (k, k+1) in one launch whenever k >= 2 is not a residual iteration (iterations 0
-/// and 1 run with zeroed K^T y / K x vectors, backend_pdhg.cu:213-216; a residual iteration as the
-/// FIRST of a pair would need y^(k-1)).  The iterate in between, x^(k+1) / y^(k+1), stays in
-/// registers: if k+1 is a residual iteration its sums are formed in the kernel, and if somebody
-/// later asks for the previous iterate (current_solution with z / w, i.e. callbacks, convergence,
-/// the end of the run) it is rebuilt by ONE single launch from the pair's inputs (RebuildPrevious).
-/// Only when iteration k+2 is a residual iteration -- it streams y^(k+1) as y_prev -- does the pair
-/// store the intermediate iterate itself.
+/// up to `budget` iterations in as few launches as the kernel family allows (NextLaunch says which); a previous iterate that a launch
+/// kept in registers is rebuilt when somebody asks for it (RebuildPrevious: current_solution with z / w, i.e. callbacks, convergence, the
+/// end of the run)
 template <typename T>
 int BackendPDHG<T>::PerformIterations(int budget) {
   // slabs with an exchange hook: a device-resident batch calls the hook itself (PerformIterationsDevice); every other path exchanges here
@@ -426,19 +423,17 @@ int BackendPDHG<T>::PerformIterationsInner(int budget) {
   if (!sol_z_.empty() && (sol_z_.size() + sol_w_.size()) * sizeof(T) > ((size_t)1 << 30)) { sol_z_.clear(); sol_w_.clear(); }
   if (spec_valid_) {
     spec_valid_ = false;
-    if (budget >= spec_count_ && k == spec_iteration_) {
-      // the launch (k .. k+g-1) already ran, into the spare buffers: exchange them in, exactly the state IterationPair / IterationGroup leaves
+    if (budget >= spec_.count && k == spec_iteration_) {
+      // the launch (k .. k+g-1) already ran, into the spare buffers: exchange them in, exactly the state IterationMulti leaves
       x_prev_.swap(x_spare_); x_.swap(x_prev_);          // x_ = x^(k+g), x_prev_ = x^k (the launch's input), spare = what x_prev_ held
       y_prev_.swap(y_spare_); y_.swap(y_prev_);
       prev_stale_ = true;
-      stale_tau_ = spec_tau_[0]; stale_sigma_ = spec_sigma_[0]; stale_theta_ = spec_theta_[0];
-      stale_count_ = spec_count_; stale_group_ = group_max_ >= 2;
-      for (int i = 1; i < spec_count_; i++) { stale_tau_more_[i] = spec_tau_[i]; stale_sigma_more_[i] = spec_sigma_[i]; stale_theta_more_[i] = spec_theta_[i]; }
-      tau_ = spec_tau_[spec_count_]; sigma_ = spec_sigma_[spec_count_]; theta_ = spec_theta_[spec_count_];
-      iteration_ += (size_t)spec_count_;
+      last_ = spec_;
+      tau_ = spec_.tau[spec_.count]; sigma_ = spec_.sigma[spec_.count]; theta_ = spec_.theta[spec_.count];
+      iteration_ += (size_t)spec_.count;
       pair_launches_++;
       spec_adopted_++;
-      return spec_count_;
+      return spec_.count;
     }
   }
   // residual-driven rules on the device: a batch of iterations, ONE host wait at its end (two- and one-iteration budgets -- a user
@@ -448,33 +443,11 @@ int BackendPDHG<T>::PerformIterationsInner(int budget) {
   if ((dev_rules_ || dev_rules_generic_) && budget >= 3 && k >= 2 &&
       !(stop_on_convergence_ && this->primal_residual_ < this->eps_primal() && this->dual_residual_ < this->eps_dual()))
     return PerformIterationsDevice(budget);
-  {
-    bool res = false;
-    const int g = GroupSize(k, budget, res);
-    if (g >= 2) {
-      IterationGroup(g, res);
-      pair_launches_++;
-      return g;
-    }
-  }
-  if (pair_kernel_ && budget >= 2 && k >= 2 && !is_residual_iteration(k)) {
-    IterationPair(is_residual_iteration(k + 2), is_residual_iteration(k + 1));
+  const Launch l = NextLaunch(k, budget);
+  if (l.count >= 2) {
+    IterationMulti(l);
     pair_launches_++;
-    return 2;
-  }
-  // gradient3d: the double-iteration kernel forms the residual sums of its second iteration but stores no intermediate
-  // iterate, so it runs unless k + 2 is a residual iteration (which streams y^(k+1)): at an even residual_iter the
-  // residual iterations are always the second of a pair
-  if (pair3d_ && budget >= 2 && k >= 2 && !is_residual_iteration(k) && !is_residual_iteration(k + 2)) {
-    IterationPair3D(is_residual_iteration(k + 1));
-    pair_launches_++;
-    return 2;
-  }
-  // 2-4 channels: the same rule (residual sums of the second iteration in the kernel, no stored intermediate iterate)
-  if (pair_mc_ && budget >= 2 && k >= 2 && !is_residual_iteration(k) && !is_residual_iteration(k + 2)) {
-    IterationPairMc(is_residual_iteration(k + 1));
-    pair_launches_++;
-    return 2;
+    return l.count;
   }
   PerformIteration();
   return 1;
@@ -491,7 +464,7 @@ void BackendPDHG<T>::RestoreRoles(const BatchMark& m) {
   place(y_, m.y, y_prev_, y_spare_); place(y_prev_, m.yp, y_spare_, y_spare_);
   if (!fused_) { place(kx_, m.kx, kx_prev_, kx_prev_); place(kty_, m.kty, kty_prev_, kty_prev_); }
   prev_stale_ = m.prev_stale;
-  stale_count_ = m.stale_count; stale_group_ = m.stale_group;
+  last_.count = m.last_count; last_.group = m.last_group;
   iteration_ = m.iteration_after;
   pair_launches_ = m.pair_launches;
   // the launches behind the stopping iteration did no work: their (near-zero) samples and launch counts are withdrawn
@@ -537,28 +510,14 @@ int BackendPDHG<T>::PerformIterationsDevice(int budget) {
       // slabs: the halo exchange when it is due (device-side, on this stream), and no launch across the next one
       if (exchange_hook_ && exchange_period_ > 0 && since_exchange_ >= exchange_period_) { exchange_hook_(); since_exchange_ = 0; }
       const int room = exchange_hook_ && exchange_period_ > 0 ? (int)std::min<size_t>((size_t)(n - done), exchange_period_ - since_exchange_) : n - done;
-      int ran = 1;
-      if (!fused_) {
-        IterationGeneric(is_residual_iteration(k));
-      } else if (bool gres = false; int g = GroupSize(k, room, gres)) {
+      const Launch l = NextLaunch(k, room);
+      if (l.count >= 2) {
         pair_launches_++;            // (counted first: the mark a residual launch leaves holds the count INCLUDING itself)
-        IterationGroup(g, gres);
-        ran = g;
-      } else if (pair_kernel_ && room >= 2 && !is_residual_iteration(k)) {
-        pair_launches_++;            // (counted first: the mark a residual launch leaves holds the count INCLUDING itself)
-        IterationPair(is_residual_iteration(k + 2), is_residual_iteration(k + 1));
-        ran = 2;
-      } else if (pair_mc_ && room >= 2 && !is_residual_iteration(k) && !is_residual_iteration(k + 2)) {     // (no stored intermediate iterate)
-        pair_launches_++;
-        IterationPairMc(is_residual_iteration(k + 1));
-        ran = 2;
-      } else if (pair3d_ && room >= 2 && k >= 2 && !is_residual_iteration(k) && !is_residual_iteration(k + 2)) {
-        pair_launches_++;
-        IterationPair3D(is_residual_iteration(k + 1));
-        ran = 2;
+        IterationMulti(l);
       } else {
-        IterationFused(is_residual_iteration(k));
+        PerformIteration();
       }
+      const int ran = l.count;
       done += ran;
       since_exchange_ += (size_t)ran;
     }
@@ -595,10 +554,10 @@ int BackendPDHG<T>::PerformIterationsDevice(int budget) {
     last_evaluated = true;
   }
   // step sizes of the last launch that ran (RebuildPrevious re-runs its first iteration): the values before its rule evaluation
-  if (last_evaluated) { stale_tau_ = (T)m.prev_tau; stale_sigma_ = (T)m.prev_sigma; stale_theta_ = (T)m.prev_theta; }
-  else { stale_tau_ = tau_; stale_sigma_ = sigma_; stale_theta_ = theta_; }
   // (every iteration of a launch inside a batch ran with the record's values of that moment)
-  for (int i = 0; i < kGroupMax; i++) { stale_tau_more_[i] = stale_tau_; stale_sigma_more_[i] = stale_sigma_; stale_theta_more_[i] = stale_theta_; }
+  for (int i = 0; i < kGroupMax; i++) {
+    last_.tau[i] = last_evaluated ? (T)m.prev_tau : tau_; last_.sigma[i] = last_evaluated ? (T)m.prev_sigma : sigma_; last_.theta[i] = last_evaluated ? (T)m.prev_theta : theta_;
+  }
   batch_marks_.clear();
   return (int)(iteration_ - k0);
 }
@@ -641,53 +600,11 @@ void BackendPDHG<T>::AbortSample(bool sampled) {
   if (!samples_.empty()) { samples_.pop_back(); if (ev_used_ >= 2) ev_used_ -= 2; }
 }
 
-template <typename T>
-void BackendPDHG<T>::IterationPair(bool store_mid, bool residuals) {
-  void* s = CurrentStream();
-  double tau[2], sigma[2], theta[2];
-  tau[0] = (double)tau_; sigma[0] = (double)sigma_; theta[0] = (double)theta_;
-  stale_tau_ = tau_; stale_sigma_ = sigma_; stale_theta_ = theta_;
-  if (opts_.stepsize_variant == kPDHGStepsAlg2) UpdateAlg2();          // step sizes of iteration k+1 (:483-488)
-  iteration_++;
-  tau[1] = (double)tau_; sigma[1] = (double)sigma_; theta[1] = (double)theta_;
-  TimedLaunch(store_mid ? (residuals ? kKernelPairMidRes : kKernelPairMid) : (residuals ? kKernelPairRes : kKernelPair), [&] {
-    if (in_device_batch_)            // step sizes from the device record (both iterations: no rule evaluation falls between them)
-      CheckHip(Api<T>::fused_iteration2_rec(&desc_pair_, store_mid ? x_spare_.data() : x_prev_.data(), store_mid ? y_spare_.data() : y_prev_.data(), x_.data(),
-                                            y_.data(), store_mid ? x_prev_.data() : nullptr, store_mid ? y_prev_.data() : nullptr, rule_rec_, 0,
-                                            residuals ? res_target() : nullptr, residuals ? workspace_ : nullptr, this->comm_ ? 0 : 1,
-                                            (unsigned long long)iteration_, rule_mirror_dev_, s), "fused_iteration2_rec");
-    else if (!store_mid)
-      CheckHip(Api<T>::fused_iteration2(&desc_pair_, x_prev_.data(), y_prev_.data(), x_.data(), y_.data(), nullptr, nullptr, tau, sigma, theta, 0,
-                                        residuals ? res_target() : nullptr, residuals ? workspace_ : nullptr, s), "fused_iteration2");
-    else
-      CheckHip(Api<T>::fused_iteration2(&desc_pair_, x_spare_.data(), y_spare_.data(), x_.data(), y_.data(), x_prev_.data(), y_prev_.data(), tau, sigma,
-                                        theta, 0, residuals ? res_target() : nullptr, residuals ? workspace_ : nullptr, s), "fused_iteration2");
-  });
-  stale_count_ = 2; stale_group_ = false;
-  if (!store_mid) {
-    x_.swap(x_prev_);        // x_ = x^(k+2); x_prev_ / y_prev_ = x^k / y^k, the pair's inputs
-    y_.swap(y_prev_);
-    prev_stale_ = true;
-  } else {
-    x_.swap(x_spare_);       // x_ = x^(k+2), x_prev_ = x^(k+1): the state two single launches leave
-    y_.swap(y_spare_);
-    prev_stale_ = false;
-  }
-  if (residuals) FinishResiduals();                                    // iteration_ == k+1 here, as in the single path
-  if (opts_.stepsize_variant == kPDHGStepsAlg2) UpdateAlg2();
-  iteration_++;
-}
-
 /// The launch PerformIterations makes at iteration k: a group never starts with a residual iteration (its sums need the iterate in
 /// front of it), never contains one except as its LAST iteration (the kernel forms the sums there), and never leaves the next residual
 /// iteration alone behind it (a single residual launch streams y^(k-1), which a group keeps in registers): with d = iterations up to and
 /// including the next residual one, g = min(budget, group_max_, d), shortened while that would leave d - g == 1 or 2.
-/// workgroups of one residual launch of the generic path (kOpLaunchSlots; PROST_OP_LAUNCH_SLOTS overrides it for measurements)
-static unsigned OpLaunchSlots() {
-  static const unsigned v = []() { const char* e = getenv("PROST_OP_LAUNCH_SLOTS"); return e && atoi(e) > 0 ? (unsigned)atoi(e) : 2048u; }();
-  return v;
-}
-
+/// 0 = no group launch, else its size; `residuals`: its last iteration is a residual iteration.
 template <typename T>
 int BackendPDHG<T>::GroupSize(size_t k, int budget, bool& residuals) const {
   residuals = false;
@@ -704,89 +621,148 @@ int BackendPDHG<T>::GroupSize(size_t k, int budget, bool& residuals) const {
   return g;
 }
 
+/// The ONE place that says what runs at iteration k when `room` iterations may run unobserved.  Several iterations share a launch
+/// whenever k >= 2 is not a residual iteration (iterations 0 and 1 run with zeroed K^T y / K x vectors, backend_pdhg.cu:213-216; a
+/// residual iteration as the FIRST of a launch would need y^(k-1)).  The iterates in between stay in registers: if the last one is a
+/// residual iteration its sums are formed in the kernel.  A pair whose successor k + 2 is a residual iteration -- it streams y^(k+1)
+/// as y_prev -- stores the iterate in between itself where the family can (gray values); the others (2-4 channels, gradient3d) run
+/// k alone then, so that at an even residual_iter their residual iterations are always the second of a pair.
 template <typename T>
-void BackendPDHG<T>::IterationGroup(int g, bool residuals) {
+typename BackendPDHG<T>::Launch BackendPDHG<T>::NextLaunch(size_t k, int room) const {
+  const Launch one{1, is_residual_iteration(k), false};
+  if (multi_ == kMultiNone || room < 2 || k < 2 || one.residuals) return one;
+  if (multi_ == kMultiGroup) {
+    bool residuals = false;
+    const int g = GroupSize(k, room, residuals);
+    return Launch{g, residuals, false};
+  }
+  const bool observed_mid = is_residual_iteration(k + 2);
+  if (observed_mid && multi_ != kMultiPair) return one;
+  return Launch{2, is_residual_iteration(k + 1), observed_mid};
+}
+
+/// the step sizes of iterations k .. k+count-1 (alg2 changes them every iteration, :483-488): tau_ / sigma_ / theta_ end as those of the last one
+template <typename T>
+void BackendPDHG<T>::StepsOfLaunch(LaunchSteps& steps, int count) {
+  steps.count = count; steps.group = multi_ == kMultiGroup;
+  for (int i = 0; i < count; i++) {
+    if (i > 0 && opts_.stepsize_variant == kPDHGStepsAlg2) UpdateAlg2();
+    steps.tau[i] = tau_; steps.sigma[i] = sigma_; steps.theta[i] = theta_;
+  }
+}
+
+/// `count` iterations from (x, y) into (x_out, y_out) with the family's multi-iteration kernel; x_mid / y_mid: where a gray-value pair
+/// stores the iterate in between.  Inside a device-resident batch the step sizes come from the device record (every iteration of the
+/// launch: no rule evaluation falls between them).  rebuild: RebuildPrevious' launch -- step sizes by value, not timed.
+template <typename T>
+void BackendPDHG<T>::LaunchMulti(int count, bool residuals, const LaunchSteps& steps, T* x_out, T* y_out, const T* x, const T* y, T* x_mid, T* y_mid, bool rebuild) {
   void* s = CurrentStream();
   double tau[kGroupMax], sigma[kGroupMax], theta[kGroupMax];
-  for (int i = 0; i < g; i++) {
-    tau[i] = (double)tau_; sigma[i] = (double)sigma_; theta[i] = (double)theta_;
-    if (i == 0) { stale_tau_ = tau_; stale_sigma_ = sigma_; stale_theta_ = theta_; }
-    else { stale_tau_more_[i] = tau_; stale_sigma_more_[i] = sigma_; stale_theta_more_[i] = theta_; }
-    if (i + 1 < g) {
-      if (opts_.stepsize_variant == kPDHGStepsAlg2) UpdateAlg2();          // step sizes of the next iteration (:483-488)
-      iteration_++;
-    }
-  }
-  // iteration_ == k + g - 1 here, the index of the launch's last iteration, as FinishResiduals expects it
-  const int kind = (residuals ? kKernelGroup2Res : kKernelGroup2) + (g - 2);
+  for (int i = 0; i < count; i++) { tau[i] = (double)steps.tau[i]; sigma[i] = (double)steps.sigma[i]; theta[i] = (double)steps.theta[i]; }
+  const bool rec = in_device_batch_ && !rebuild;
+  const int rule = this->comm_ ? 0 : 1;
+  const unsigned long long it = (unsigned long long)iteration_;        // the index of the launch's last iteration
+  double* sums = residuals ? res_target() : nullptr;
+  void* ws = residuals ? workspace_ : nullptr;
+  const int kind = rebuild ? kUntimed : multi_ == kMultiGroup ? (residuals ? kKernelGroup2Res : kKernelGroup2) + (count - 2)
+                   : x_mid ? (residuals ? kKernelPairMidRes : kKernelPairMid) : (residuals ? kKernelPairRes : kKernelPair);
   TimedLaunch(kind, [&] {
-    if (in_device_batch_)            // step sizes from the device record (every iteration of the launch: no rule evaluation falls between them)
-      CheckHip(Api<T>::fused_iterationk_rec(&desc_pair_, g, x_prev_.data(), y_prev_.data(), x_.data(), y_.data(), rule_rec_, 0, residuals ? res_target() : nullptr,
-                                            residuals ? workspace_ : nullptr, this->comm_ ? 0 : 1, (unsigned long long)iteration_, rule_mirror_dev_, s), "fused_iterationk_rec");
-    else
-      CheckHip(Api<T>::fused_iterationk(&desc_pair_, g, x_prev_.data(), y_prev_.data(), x_.data(), y_.data(), tau, sigma, theta, 0,
-                                        residuals ? res_target() : nullptr, residuals ? workspace_ : nullptr, s), "fused_iterationk");
+    switch (multi_) {
+      case kMultiPair:
+        if (rec) CheckHip(Api<T>::fused_iteration2_rec(&desc_pair_, x_out, y_out, x, y, x_mid, y_mid, rule_rec_, 0, sums, ws, rule, it, rule_mirror_dev_, s), "fused_iteration2_rec");
+        else CheckHip(Api<T>::fused_iteration2(&desc_pair_, x_out, y_out, x, y, x_mid, y_mid, tau, sigma, theta, 0, sums, ws, s), "fused_iteration2");
+        break;
+      case kMultiGroup:
+        if (rec) CheckHip(Api<T>::fused_iterationk_rec(&desc_pair_, count, x_out, y_out, x, y, rule_rec_, 0, sums, ws, rule, it, rule_mirror_dev_, s), "fused_iterationk_rec");
+        else CheckHip(Api<T>::fused_iterationk(&desc_pair_, count, x_out, y_out, x, y, tau, sigma, theta, 0, sums, ws, s), "fused_iterationk");
+        break;
+      case kMultiMc:
+        if (rec) CheckHip(Api<T>::fused_iteration_mc_x2_rec(&desc_pair_, x_out, y_out, x, y, rule_rec_, 0, sums, ws, rule, it, rule_mirror_dev_, s), "fused_iteration_mc_x2_rec");
+        else CheckHip(Api<T>::fused_iteration_mc_x2(&desc_pair_, x_out, y_out, x, y, tau, sigma, theta, 0, sums, ws, s), "fused_iteration_mc_x2");
+        break;
+      case kMultiVol:
+        if (rec) CheckHip(Api<T>::fused_iteration3d_x2_rec(&desc_, x_out, y_out, x, y, rule_rec_, 0, sums, ws, rule, it, rule_mirror_dev_, s), "fused_iteration3d_x2_rec");
+        else CheckHip(Api<T>::fused_iteration3d_x2(&desc_, x_out, y_out, x, y, tau, sigma, theta, 0, sums, ws, s), "fused_iteration3d_x2");
+        break;
+      case kMultiNone: break;
+    }
   });
-  x_.swap(x_prev_);        // x_ = x^(k+g); x_prev_ / y_prev_ = x^k / y^k, the launch's inputs
-  y_.swap(y_prev_);
-  prev_stale_ = true; stale_count_ = g; stale_group_ = true;
-  if (residuals) FinishResiduals();
-  if (opts_.stepsize_variant == kPDHGStepsAlg2) UpdateAlg2();
-  iteration_++;
 }
 
+/// ONE iteration from (x, y) into (x_new, y_new) in the family's single-iteration form.  One kernel: x_new never round-trips through
+/// HBM (2-D: 7 instead of 11 values per pixel and channel, 3-D: 9 instead of 14 per voxel; residual iterations add the y_prev stream
+/// and the four sums); gradient3d with single_pw_: the planes across the wavefronts of a workgroup on non-residual iterations, x_new of
+/// the plane above comes through LDS.  Two passes: x_new goes through HBM.  The reference's kty_ is K^T y^k except at k = 0 (zero
+/// vector, :213), kty_prev_ is K^T y^(k-1) except at k <= 1, kx_prev_ is K x^k except at k = 0 (:216): the use_* flags.
+/// rebuild: RebuildPrevious' launch -- an iteration k >= 2 without sums, step sizes by value, not timed.
 template <typename T>
-void BackendPDHG<T>::IterationPair3D(bool residuals) {
-  double tau[2], sigma[2], theta[2];
-  tau[0] = (double)tau_; sigma[0] = (double)sigma_; theta[0] = (double)theta_;
-  stale_tau_ = tau_; stale_sigma_ = sigma_; stale_theta_ = theta_;
-  if (opts_.stepsize_variant == kPDHGStepsAlg2) UpdateAlg2();          // step sizes of iteration k+1 (:483-488)
-  iteration_++;
-  tau[1] = (double)tau_; sigma[1] = (double)sigma_; theta[1] = (double)theta_;
-  TimedLaunch(residuals ? kKernelPairRes : kKernelPair, [&] {
-    if (in_device_batch_)
-      CheckHip(Api<T>::fused_iteration3d_x2_rec(&desc_, x_prev_.data(), y_prev_.data(), x_.data(), y_.data(), rule_rec_, 0, residuals ? res_target() : nullptr,
-                                                residuals ? workspace_ : nullptr, this->comm_ ? 0 : 1, (unsigned long long)iteration_, rule_mirror_dev_, CurrentStream()),
-               "fused_iteration3d_x2_rec");
-    else
-    CheckHip(Api<T>::fused_iteration3d_x2(&desc_, x_prev_.data(), y_prev_.data(), x_.data(), y_.data(), tau, sigma, theta, 0,
-                                          residuals ? res_target() : nullptr, residuals ? workspace_ : nullptr, CurrentStream()), "fused_iteration3d_x2");
+void BackendPDHG<T>::LaunchSingle(T* x_new, T* y_new, const T* x, const T* y, const T* y_prev, T tau_t, T sigma_t, T theta_t, bool residuals, bool rebuild) {
+  void* s = CurrentStream();
+  const double tau = (double)tau_t, sigma = (double)sigma_t, theta = (double)theta_t;
+  const int use_kty = rebuild || iteration_ >= 1 ? 1 : 0, use_kx_prev = use_kty;
+  const int use_kty_prev = rebuild ? (single_ == kTwoPass ? 0 : 1) : iteration_ >= 2 ? 1 : 0;      // (feeds the sums only; the primal pass of a rebuild has no y_prev)
+  const bool rec = in_device_batch_ && !rebuild;
+  const int rule = this->comm_ ? 0 : 1;
+  const unsigned long long it = (unsigned long long)iteration_;
+  double* sums = residuals ? res_target() : nullptr;
+  void* ws = residuals ? workspace_ : nullptr;
+  const int kind = rebuild ? kUntimed : residuals ? kKernelIterRes : kKernelIter;
+  if (single_ == kTwoPass) {
+    TimedLaunch(rebuild ? kUntimed : kKernelPrimal, [&] {
+      CheckHip(Api<T>::fused_primal(&desc_, x_new, x, y, y_prev, tau, use_kty, use_kty_prev, sums ? sums + 2 : nullptr, workspace_, s), "fused_primal");
+    });
+    TimedLaunch(rebuild ? kUntimed : kKernelDual, [&] {
+      CheckHip(Api<T>::fused_dual(&desc_, y_new, y, x_new, x, sigma, theta, use_kx_prev, sums, workspace_, s), "fused_dual");
+    });
+    return;
+  }
+  TimedLaunch(kind, [&] {
+    switch (single_) {
+      case kSingleGray:
+        if (rec) CheckHip(Api<T>::fused_iteration_rec(&desc_, x_new, y_new, x, y, y_prev, rule_rec_, use_kty, use_kx_prev, use_kty_prev, 0, sums, ws, rule, it, rule_mirror_dev_, s), "fused_iteration_rec");
+        else CheckHip(Api<T>::fused_iteration(&desc_, x_new, y_new, x, y, y_prev, tau, sigma, theta, use_kty, use_kx_prev, use_kty_prev, 0, sums, ws, s), "fused_iteration");
+        break;
+      case kSingleMc:
+        if (rec) CheckHip(Api<T>::fused_iteration_mc_rec(&desc_, x_new, y_new, x, y, y_prev, rule_rec_, use_kty, use_kx_prev, use_kty_prev, 0, sums, ws, rule, it, rule_mirror_dev_, s), "fused_iteration_mc_rec");
+        else CheckHip(Api<T>::fused_iteration_mc(&desc_, x_new, y_new, x, y, y_prev, tau, sigma, theta, use_kty, use_kx_prev, use_kty_prev, 0, sums, ws, s), "fused_iteration_mc");
+        break;
+      case kSingleVol:
+        if (single_pw_ && !residuals && !rebuild) {
+          if (rec) CheckHip(Api<T>::fused_iteration3d_pw_rec(&desc_, x_new, y_new, x, y, rule_rec_, use_kty, use_kx_prev, 0, 0, s), "fused_iteration3d_pw_rec");
+          else CheckHip(Api<T>::fused_iteration3d_pw(&desc_, x_new, y_new, x, y, tau, sigma, theta, use_kty, use_kx_prev, 0, 0, s), "fused_iteration3d_pw");
+        }
+        else if (rec) CheckHip(Api<T>::fused_iteration3d_rec(&desc_, x_new, y_new, x, y, y_prev, rule_rec_, use_kty, use_kx_prev, use_kty_prev, 0, sums, ws, rule, it, rule_mirror_dev_, s), "fused_iteration3d_rec");
+        else CheckHip(Api<T>::fused_iteration3d(&desc_, x_new, y_new, x, y, y_prev, tau, sigma, theta, use_kty, use_kx_prev, use_kty_prev, 0, sums, ws, s), "fused_iteration3d");
+        break;
+      case kTwoPass: break;
+    }
   });
-  x_.swap(x_prev_);        // x_ = x^(k+2); x_prev_ / y_prev_ = x^k / y^k, the pair's inputs
-  y_.swap(y_prev_);
-  prev_stale_ = true; stale_count_ = 2; stale_group_ = false;
-  if (residuals) FinishResiduals();                                    // iteration_ == k+1 here, as in the single path
-  if (opts_.stepsize_variant == kPDHGStepsAlg2) UpdateAlg2();
-  iteration_++;
 }
 
+/// iterations k .. k + l.count - 1 in one launch (NextLaunch)
 template <typename T>
-void BackendPDHG<T>::IterationPairMc(bool residuals) {
-  double tau[2], sigma[2], theta[2];
-  tau[0] = (double)tau_; sigma[0] = (double)sigma_; theta[0] = (double)theta_;
-  stale_tau_ = tau_; stale_sigma_ = sigma_; stale_theta_ = theta_;
-  if (opts_.stepsize_variant == kPDHGStepsAlg2) UpdateAlg2();          // step sizes of iteration k+1 (:483-488)
-  iteration_++;
-  tau[1] = (double)tau_; sigma[1] = (double)sigma_; theta[1] = (double)theta_;
-  TimedLaunch(residuals ? kKernelPairRes : kKernelPair, [&] {
-    if (in_device_batch_)
-      CheckHip(Api<T>::fused_iteration_mc_x2_rec(&desc_pair_, x_prev_.data(), y_prev_.data(), x_.data(), y_.data(), rule_rec_, 0, residuals ? res_target() : nullptr,
-                                                 residuals ? workspace_ : nullptr, this->comm_ ? 0 : 1, (unsigned long long)iteration_, rule_mirror_dev_, CurrentStream()),
-               "fused_iteration_mc_x2_rec");
-    else
-    CheckHip(Api<T>::fused_iteration_mc_x2(&desc_pair_, x_prev_.data(), y_prev_.data(), x_.data(), y_.data(), tau, sigma, theta, 0,
-                                           residuals ? res_target() : nullptr, residuals ? workspace_ : nullptr, CurrentStream()), "fused_iteration_mc_x2");
-  });
-  x_.swap(x_prev_);        // x_ = x^(k+2); x_prev_ / y_prev_ = x^k / y^k, the pair's inputs
-  y_.swap(y_prev_);
-  prev_stale_ = true; stale_count_ = 2; stale_group_ = false;
-  if (residuals) FinishResiduals();                                    // iteration_ == k+1 here, as in the single path
+void BackendPDHG<T>::IterationMulti(const Launch& l) {
+  StepsOfLaunch(last_, l.count);
+  iteration_ += (size_t)(l.count - 1);       // the index of the launch's last iteration, as the kernels' record and FinishResiduals expect it
+  if (l.store_mid) {
+    LaunchMulti(2, l.residuals, last_, x_spare_.data(), y_spare_.data(), x_.data(), y_.data(), x_prev_.data(), y_prev_.data(), false);
+    x_.swap(x_spare_);       // x_ = x^(k+2), x_prev_ = x^(k+1): the state two single launches leave
+    y_.swap(y_spare_);
+  } else {
+    LaunchMulti(l.count, l.residuals, last_, x_prev_.data(), y_prev_.data(), x_.data(), y_.data(), nullptr, nullptr, false);
+    x_.swap(x_prev_);        // x_ = x^(k+count); x_prev_ / y_prev_ = x^k / y^k, the launch's inputs
+    y_.swap(y_prev_);
+  }
+  prev_stale_ = !l.store_mid;
+  if (l.residuals) FinishResiduals();
   if (opts_.stepsize_variant == kPDHGStepsAlg2) UpdateAlg2();
   iteration_++;
 }
 
-/// x_prev_ / y_prev_ hold x^k, y^k (inputs of the last pair launch), x_ / y_ = x^(k+2), y^(k+2): one
-/// single-iteration launch with the step sizes of iteration k rebuilds x^(k+1), y^(k+1) bit for bit.
+/// x_prev_ / y_prev_ hold x^k, y^k (inputs of the last multi-iteration launch), x_ / y_ = x^(k+count): its first count - 1 iterations
+/// are run again from them, with the step sizes they ran with.  A group re-runs as a shorter group in the same arithmetic (a launch of
+/// K iterations equals any partition of it into shorter launches bit for bit); a pair re-runs its first iteration in the family's
+/// single-iteration form, which rebuilds x^(k+1), y^(k+1) of an exact-class pair bit for bit.
 template <typename T>
 void BackendPDHG<T>::RebuildPrevious() {
   spec_valid_ = false;               // (the spare buffers are about to be written, or the state to be looked at)
@@ -794,136 +770,36 @@ void BackendPDHG<T>::RebuildPrevious() {
   last_end_ = kNoEvent;
   if (x_spare_.size() != x_.size()) x_spare_.resize(x_.size());
   if (y_spare_.size() != y_.size()) y_spare_.resize(y_.size());
-  if (stale_group_) {
-    // a group of stale_count_ iterations: the iterate in front of its last one is stale_count_ - 1 iterations behind the inputs, in the
-    // same arithmetic (a launch of K iterations equals any partition of it into shorter launches bit for bit)
-    double tau[kGroupMax], sigma[kGroupMax], theta[kGroupMax];
-    tau[0] = (double)stale_tau_; sigma[0] = (double)stale_sigma_; theta[0] = (double)stale_theta_;
-    for (int i = 1; i < stale_count_ - 1; i++) { tau[i] = (double)stale_tau_more_[i]; sigma[i] = (double)stale_sigma_more_[i]; theta[i] = (double)stale_theta_more_[i]; }
-    CheckHip(Api<T>::fused_iterationk(&desc_pair_, stale_count_ - 1, x_spare_.data(), y_spare_.data(), x_prev_.data(), y_prev_.data(), tau, sigma, theta, 0,
-                                      nullptr, nullptr, CurrentStream()), "fused_iterationk");
-  } else
-  if (pair_mc_ && single_mc_)
-    CheckHip(Api<T>::fused_iteration_mc(&desc_, x_spare_.data(), y_spare_.data(), x_prev_.data(), y_prev_.data(), nullptr, (double)stale_tau_,
-                                        (double)stale_sigma_, (double)stale_theta_, 1, 1, 1, 0, nullptr, nullptr, CurrentStream()), "fused_iteration_mc");
-  else if (pair3d_ && single3d_)
-    CheckHip(Api<T>::fused_iteration3d(&desc_, x_spare_.data(), y_spare_.data(), x_prev_.data(), y_prev_.data(), nullptr, (double)stale_tau_,
-                                       (double)stale_sigma_, (double)stale_theta_, 1, 1, 1, 0, nullptr, nullptr, CurrentStream()), "fused_iteration3d");
-  else if (pair3d_ || (pair_mc_ && !single_kernel_)) {        // heights the one-kernel iterations do not take: the two passes
-    CheckHip(Api<T>::fused_primal(&desc_, x_spare_.data(), x_prev_.data(), y_prev_.data(), nullptr, (double)stale_tau_, 1, 0, nullptr, workspace_,
-                                  CurrentStream()), "fused_primal");
-    CheckHip(Api<T>::fused_dual(&desc_, y_spare_.data(), y_prev_.data(), x_spare_.data(), x_prev_.data(), (double)stale_sigma_, (double)stale_theta_, 1,
-                                nullptr, workspace_, CurrentStream()), "fused_dual");
-  } else
-  CheckHip(Api<T>::fused_iteration(&desc_, x_spare_.data(), y_spare_.data(), x_prev_.data(), y_prev_.data(), nullptr, (double)stale_tau_,
-                                   (double)stale_sigma_, (double)stale_theta_, 1, 1, 1, 0, nullptr, nullptr, CurrentStream()), "fused_iteration");
+  if (last_.group) LaunchMulti(last_.count - 1, false, last_, x_spare_.data(), y_spare_.data(), x_prev_.data(), y_prev_.data(), nullptr, nullptr, true);
+  // KNOWN DEFECT: the single-iteration kernels compute exactly, also behind a tolerance-class 2-4 channel / gradient3d pair (kMultiMc, kMultiVol with arith FMAD)
+  else LaunchSingle(x_spare_.data(), y_spare_.data(), x_prev_.data(), y_prev_.data(), nullptr, last_.tau[0], last_.sigma[0], last_.theta[0], false, true);
   x_prev_.swap(x_spare_);
   y_prev_.swap(y_spare_);
   prev_stale_ = false;
 }
 
-/// two kernels: x_ / y_ ping-pong with x_prev_ / y_prev_
+/// one iteration: x_ / y_ ping-pong with x_prev_ / y_prev_.  At entry x_ = x^k, y_ = y^k, y_prev_ = y^(k-1); outputs go to the
+/// previous-iterate buffers, except that the one-kernel forms cannot overwrite y_prev_ on residual iterations (the kernel still
+/// reads it): y_new goes to y_spare_ then.
 template <typename T>
 void BackendPDHG<T>::IterationFused(bool res) {
-  void* s = CurrentStream();
-  // at entry: x_ = x^k, y_ = y^k, y_prev_ = y^(k-1).  The reference's kty_ is K^T y^k except at
-  // k = 0 (zero vector, :213); kty_prev_ is K^T y^(k-1) except at k <= 1 (zero vector).
-  if (single_kernel_) {
-    if (res) RebuildPrevious();      // the residual kernel streams y^(k-1)
-    // ONE kernel per iteration, x_new never round-trips through HBM (7 floats/pixel; residual
-    // iterations add the y_prev stream and the four residual sums).  y_new cannot overwrite
-    // y_prev_ on residual iterations (the kernel still reads it), so it goes to y_spare_.
-    T* y_out = res ? y_spare_.data() : y_prev_.data();
-    TimedLaunch(res ? kKernelIterRes : kKernelIter, [&] {
-      if (in_device_batch_)
-        CheckHip(Api<T>::fused_iteration_rec(&desc_, x_prev_.data(), y_out, x_.data(), y_.data(), res ? y_prev_.data() : nullptr, rule_rec_,
-                                             iteration_ >= 1 ? 1 : 0, iteration_ >= 1 ? 1 : 0, iteration_ >= 2 ? 1 : 0, 0, res ? res_target() : nullptr,
-                                             res ? workspace_ : nullptr, this->comm_ ? 0 : 1, (unsigned long long)iteration_, rule_mirror_dev_, s), "fused_iteration_rec");
-      else
-      CheckHip(Api<T>::fused_iteration(&desc_, x_prev_.data(), y_out, x_.data(), y_.data(), res ? y_prev_.data() : nullptr, (double)tau_,
-                                       (double)sigma_, (double)theta_, iteration_ >= 1 ? 1 : 0, iteration_ >= 1 ? 1 : 0,
-                                       iteration_ >= 2 ? 1 : 0, 0, res ? res_target() : nullptr, res ? workspace_ : nullptr, s), "fused_iteration");
-    });
-    x_.swap(x_prev_);
-    if (res) { y_prev_.swap(y_spare_); }     // y_prev_ now holds y^(k+1); swapped into y_ below
-    y_.swap(y_prev_);
-    prev_stale_ = false;
-    if (res) FinishResiduals();
-    if (opts_.stepsize_variant == kPDHGStepsAlg2) UpdateAlg2();
-    iteration_++;
-    return;
-  }
-  if (single3d_) {
-    // gradient3d: one kernel, x_new stays in registers (9 instead of 14 values per voxel; residual iterations add the
-    // y_prev stream of the own plane and the four sums).  Outputs go to the previous-iterate buffers, which a
-    // non-residual iteration does not read; on residual iterations y_new goes to y_spare_ (the kernel still reads y_prev_).
-    if (res) RebuildPrevious();      // the residual kernel streams y^(k-1)
-    T* y_out = res ? y_spare_.data() : y_prev_.data();
-    TimedLaunch(res ? kKernelIterRes : kKernelIter, [&] {
-      if (in_device_batch_ && single3d_pw_ && !res)
-        CheckHip(Api<T>::fused_iteration3d_pw_rec(&desc_, x_prev_.data(), y_out, x_.data(), y_.data(), rule_rec_, iteration_ >= 1 ? 1 : 0, iteration_ >= 1 ? 1 : 0, 0, 0, s),
-                 "fused_iteration3d_pw_rec");
-      else if (in_device_batch_)
-        CheckHip(Api<T>::fused_iteration3d_rec(&desc_, x_prev_.data(), y_out, x_.data(), y_.data(), res ? y_prev_.data() : nullptr, rule_rec_, iteration_ >= 1 ? 1 : 0,
-                                               iteration_ >= 1 ? 1 : 0, iteration_ >= 2 ? 1 : 0, 0, res ? res_target() : nullptr, res ? workspace_ : nullptr,
-                                               this->comm_ ? 0 : 1, (unsigned long long)iteration_, rule_mirror_dev_, s), "fused_iteration3d_rec");
-      else if (single3d_pw_ && !res)        // planes across the wavefronts of a workgroup: x_new of the plane above comes through LDS
-        CheckHip(Api<T>::fused_iteration3d_pw(&desc_, x_prev_.data(), y_out, x_.data(), y_.data(), (double)tau_, (double)sigma_, (double)theta_,
-                                              iteration_ >= 1 ? 1 : 0, iteration_ >= 1 ? 1 : 0, 0, 0, s), "fused_iteration3d_pw");
-      else
-      CheckHip(Api<T>::fused_iteration3d(&desc_, x_prev_.data(), y_out, x_.data(), y_.data(), res ? y_prev_.data() : nullptr, (double)tau_, (double)sigma_,
-                                         (double)theta_, iteration_ >= 1 ? 1 : 0, iteration_ >= 1 ? 1 : 0, iteration_ >= 2 ? 1 : 0, 0,
-                                         res ? res_target() : nullptr, res ? workspace_ : nullptr, s), "fused_iteration3d");
-    });
-    x_.swap(x_prev_);
-    if (res) y_prev_.swap(y_spare_);
-    y_.swap(y_prev_);
-    prev_stale_ = false;
-    if (res) FinishResiduals();
-    if (opts_.stepsize_variant == kPDHGStepsAlg2) UpdateAlg2();
-    iteration_++;
-    return;
-  }
-  if (single_mc_) {
-    // gradient2d with 3 / 4 channels: one kernel, the channels on the wavefronts of a workgroup (7 instead of 11 values per
-    // pixel and channel; residual iterations add the y_prev stream and the four sums, y_new then goes to y_spare_)
-    if (res) RebuildPrevious();      // the residual kernel streams y^(k-1)
-    T* y_out = res ? y_spare_.data() : y_prev_.data();
-    TimedLaunch(res ? kKernelIterRes : kKernelIter, [&] {
-      if (in_device_batch_)
-        CheckHip(Api<T>::fused_iteration_mc_rec(&desc_, x_prev_.data(), y_out, x_.data(), y_.data(), res ? y_prev_.data() : nullptr, rule_rec_,
-                                                iteration_ >= 1 ? 1 : 0, iteration_ >= 1 ? 1 : 0, iteration_ >= 2 ? 1 : 0, 0, res ? res_target() : nullptr,
-                                                res ? workspace_ : nullptr, this->comm_ ? 0 : 1, (unsigned long long)iteration_, rule_mirror_dev_, s), "fused_iteration_mc_rec");
-      else
-      CheckHip(Api<T>::fused_iteration_mc(&desc_, x_prev_.data(), y_out, x_.data(), y_.data(), res ? y_prev_.data() : nullptr, (double)tau_, (double)sigma_,
-                                          (double)theta_, iteration_ >= 1 ? 1 : 0, iteration_ >= 1 ? 1 : 0, iteration_ >= 2 ? 1 : 0, 0,
-                                          res ? res_target() : nullptr, res ? workspace_ : nullptr, s), "fused_iteration_mc");
-    });
-    x_.swap(x_prev_);
-    if (res) y_prev_.swap(y_spare_);
-    y_.swap(y_prev_);
-    prev_stale_ = false;
-    if (res) FinishResiduals();
-    if (opts_.stepsize_variant == kPDHGStepsAlg2) UpdateAlg2();
-    iteration_++;
-    return;
-  }
-  if (res) RebuildPrevious();        // the residual primal pass streams y^(k-1)
-  prev_stale_ = false;
-  TimedLaunch(kKernelPrimal, [&] {
-    CheckHip(Api<T>::fused_primal(&desc_, x_prev_.data(), x_.data(), y_.data(), y_prev_.data(), (double)tau_, iteration_ >= 1 ? 1 : 0,
-                                  iteration_ >= 2 ? 1 : 0, res ? res_target() + 2 : nullptr, workspace_, s), "fused_primal");
-  });
+  if (res) RebuildPrevious();        // the residual launch streams y^(k-1)
+  const bool third = res && single_ != kTwoPass;
+  LaunchSingle(x_prev_.data(), third ? y_spare_.data() : y_prev_.data(), x_.data(), y_.data(), res || single_ == kTwoPass ? y_prev_.data() : nullptr, tau_, sigma_,
+               theta_, res, false);
   x_.swap(x_prev_);                        // x_ = x^(k+1), x_prev_ = x^k       (:334)
-  // kx_prev_ of the reference is K x^k except at k = 0 (zero vector, :216)
-  TimedLaunch(kKernelDual, [&] {
-    CheckHip(Api<T>::fused_dual(&desc_, y_prev_.data(), y_.data(), x_.data(), x_prev_.data(), (double)sigma_, (double)theta_,
-                                iteration_ >= 1 ? 1 : 0, res ? res_target() : nullptr, workspace_, s), "fused_dual");
-  });
+  if (third) y_prev_.swap(y_spare_);       // y_prev_ now holds y^(k+1); swapped into y_ below
   y_.swap(y_prev_);                        // y_ = y^(k+1), y_prev_ = y^k       (:366)
+  prev_stale_ = false;
   if (res) FinishResiduals();
   if (opts_.stepsize_variant == kPDHGStepsAlg2) UpdateAlg2();
   iteration_++;
+}
+
+/// workgroups of one residual launch of the generic path (kOpLaunchSlots; PROST_OP_LAUNCH_SLOTS overrides it for measurements)
+static unsigned OpLaunchSlots() {
+  static const unsigned v = []() { const char* e = getenv("PROST_OP_LAUNCH_SLOTS"); return e && atoi(e) > 0 ? (unsigned)atoi(e) : 2048u; }();
+  return v;
 }
 
 /// The operator as a table of sparse (CSR arrays or row patterns) and gradient blocks for the operator sources of the prox kernels
@@ -1121,9 +997,8 @@ void BackendPDHG<T>::FinishResiduals() {
                             kx_.data(), kx_prev_.data(), op_fused_ ? kty_.data() : kty_prev_.data(), op_fused_ ? kty_prev_.data() : kty_.data()});
     // kernel timing: launches enqueued behind a stopping iteration return at once -- their samples must not enter the averages
     // (RestoreRoles drops everything recorded after the mark it returns to)
-    static_assert(kKernelKinds == 14, "BatchMark::launches holds one counter per kernel kind");
     batch_marks_.back().samples = samples_.size(); batch_marks_.back().ev_used = ev_used_;
-    batch_marks_.back().stale_count = stale_count_; batch_marks_.back().stale_group = stale_group_;
+    batch_marks_.back().last_count = last_.count; batch_marks_.back().last_group = last_.group;
     for (int kk = 0; kk < kKernelKinds; kk++) batch_marks_.back().launches[kk] = launches_[kk];
     batch_last_launch_evaluated_ = true;
     return;
@@ -1145,7 +1020,7 @@ void BackendPDHG<T>::FinishResiduals() {
       CheckHip(prost_hip_memcpy_d2h(res_host_, res_dev_, 4 * sizeof(double), s), "memcpy_d2h");
     }
   }
-  else if (opts_.allow_speculation && pair_kernel_) {
+  else if (opts_.allow_speculation && gray_multi()) {
     if (!ev_res_local_) CheckHip(prost_hip_event_create(&ev_res_local_), "event_create");
     CheckHip(prost_hip_event_record(ev_res_local_, s), "event_record");
   }
@@ -1157,44 +1032,24 @@ template <typename T>
 bool BackendPDHG<T>::CanSpeculate() const {
   // (what the host is about to wait for: the event behind the residual launch, or -- with a communicator -- the one behind the
   // all-reduce on the side stream)
-  if (!opts_.allow_speculation || !pair_kernel_ || owned_x1_ != 0 || !(resolve_on_side_ || (ev_res_local_ && !this->comm_)) || spec_valid_) return false;
+  if (!opts_.allow_speculation || !gray_multi() || owned_x1_ != 0 || !(resolve_on_side_ || (ev_res_local_ && !this->comm_)) || spec_valid_) return false;
   if (opts_.stepsize_variant != kPDHGStepsAlg1 && opts_.stepsize_variant != kPDHGStepsAlg2) return false;
-  const size_t k = iteration_;
-  if (group_max_ >= 2) {
-    // a PLAIN group must be what PerformIterations would launch next with a large budget (a smaller budget drops the speculation)
-    bool res = false;
-    const int g = GroupSize(k, kGroupMax, res);
-    if (g < 2 || res) return false;
-    return x_spare_.size() == x_.size() && y_spare_.size() == y_.size();
-  }
-  // a PLAIN pair must be what PerformIterations(budget >= 2) would launch next: no residual sums, no stored intermediate iterate
-  if (k < 2 || is_residual_iteration(k) || is_residual_iteration(k + 1) || is_residual_iteration(k + 2)) return false;
+  // a PLAIN pair / group must be what PerformIterations would launch next with a large budget (a smaller budget drops the speculation):
+  // no residual sums, no stored intermediate iterate
+  const Launch l = NextLaunch(iteration_, kGroupMax);
+  if (l.count < 2 || l.residuals || l.store_mid) return false;
   return x_spare_.size() == x_.size() && y_spare_.size() == y_.size();
 }
 
 template <typename T>
 void BackendPDHG<T>::Speculate() {
-  double tau[kGroupMax], sigma[kGroupMax], theta[kGroupMax];
   const T t0 = tau_, s0 = sigma_, th0 = theta_;
-  bool res = false;
-  const int g = group_max_ >= 2 ? GroupSize(iteration_, kGroupMax, res) : 2;
-  spec_count_ = g;
-  for (int i = 0; i <= g; i++) {
-    spec_tau_[i] = tau_; spec_sigma_[i] = sigma_; spec_theta_[i] = theta_;
-    if (i < g && opts_.stepsize_variant == kPDHGStepsAlg2) UpdateAlg2();
-  }
+  const int g = NextLaunch(iteration_, kGroupMax).count;
+  StepsOfLaunch(spec_, g);
+  if (opts_.stepsize_variant == kPDHGStepsAlg2) UpdateAlg2();
+  spec_.tau[g] = tau_; spec_.sigma[g] = sigma_; spec_.theta[g] = theta_;          // ... and after the launch
   tau_ = t0; sigma_ = s0; theta_ = th0;                  // nothing observable changes until the results are adopted
-  for (int i = 0; i < g; i++) { tau[i] = (double)spec_tau_[i]; sigma[i] = (double)spec_sigma_[i]; theta[i] = (double)spec_theta_[i]; }
-  if (group_max_ >= 2)
-    TimedLaunch(kKernelGroup2 + (g - 2), [&] {
-      CheckHip(Api<T>::fused_iterationk(&desc_pair_, g, x_spare_.data(), y_spare_.data(), x_.data(), y_.data(), tau, sigma, theta, 0, nullptr, nullptr,
-                                        CurrentStream()), "fused_iterationk");
-    });
-  else
-  TimedLaunch(kKernelPair, [&] {
-    CheckHip(Api<T>::fused_iteration2(&desc_pair_, x_spare_.data(), y_spare_.data(), x_.data(), y_.data(), nullptr, nullptr, tau, sigma, theta, 0,
-                                      nullptr, nullptr, CurrentStream()), "fused_iteration2");
-  });
+  LaunchMulti(g, false, spec_, x_spare_.data(), y_spare_.data(), x_.data(), y_.data(), nullptr, nullptr, false);
   spec_iteration_ = iteration_;
   spec_valid_ = true;
   spec_launched_++;            // (KernelTimes counts this launch under the pair kernel whether or not it is adopted: it ran; pair_launches_
@@ -1348,10 +1203,10 @@ void BackendPDHG<T>::KernelTimes(std::vector<typename Backend<T>::KernelTime>& o
   }
   const bool d3 = desc_.is3d != 0;
   const char* names[kKernelKinds] = {d3 ? "fused_primal3d_kernel" : "fused_primal2d_kernel", d3 ? "fused_dual3d_kernel" : "fused_dual2d_kernel",
-                                     d3 ? "fused_iter3d_kernel" : single_mc_ ? "fused_iter2d_mc_kernel" : "fused_iter2d_kernel",
+                                     d3 ? "fused_iter3d_kernel" : single_ == kSingleMc ? "fused_iter2d_mc_kernel" : "fused_iter2d_kernel",
                                      d3 ? "fused_iter3d_kernel+residuals" : "fused_iter2d_kernel+residuals",
-                                     d3 ? "fused_iter3d_x2_kernel" : pair_mc_ ? "fused_iter2d_mc_x2_kernel" : "fused_iter2d_x2_kernel", "fused_iter2d_x2_kernel+mid",
-                                     d3 ? "fused_iter3d_x2_kernel+residuals" : pair_mc_ ? "fused_iter2d_mc_x2_kernel+residuals" : "fused_iter2d_x2_kernel+residuals",
+                                     d3 ? "fused_iter3d_x2_kernel" : multi_ == kMultiMc ? "fused_iter2d_mc_x2_kernel" : "fused_iter2d_x2_kernel", "fused_iter2d_x2_kernel+mid",
+                                     d3 ? "fused_iter3d_x2_kernel+residuals" : multi_ == kMultiMc ? "fused_iter2d_mc_x2_kernel+residuals" : "fused_iter2d_x2_kernel+residuals",
                                      "fused_iter2d_x2_kernel+mid+residuals",
                                      "fused_iter2d_xk_kernel<2>", "fused_iter2d_xk_kernel<3>", "fused_iter2d_xk_kernel<4>",
                                      "fused_iter2d_xk_kernel<2>+residuals", "fused_iter2d_xk_kernel<3>+residuals", "fused_iter2d_xk_kernel<4>+residuals"};
@@ -1359,9 +1214,9 @@ void BackendPDHG<T>::KernelTimes(std::vector<typename Backend<T>::KernelTime>& o
   for (int k = 0; k < kKernelKinds; k++) {
     if (!cnt[k]) continue;
     const int cols = k >= kKernelGroup2 ? prost_hip_fused_iterationk_chunk_cols(&desc_pair_, dtype_id<T>(), iters[k], k >= kKernelGroup2Res)
-                     : k >= kKernelPair && pair_kernel_ ? prost_hip_fused_iteration2_chunk_cols(&desc_pair_, dtype_id<T>(), k == kKernelPairRes || k == kKernelPairMidRes)
-                     : (k == kKernelPair || k == kKernelPairRes) && pair3d_ ? prost_hip_fused_iteration3d_x2_chunk_cols(&desc_, dtype_id<T>(), k == kKernelPairRes)
-                     : (k == kKernelPair || k == kKernelPairRes) && pair_mc_ ? prost_hip_fused_iteration_mc_x2_chunk_cols(&desc_pair_, dtype_id<T>(), k == kKernelPairRes) : 0;
+                     : k >= kKernelPair && gray_multi() ? prost_hip_fused_iteration2_chunk_cols(&desc_pair_, dtype_id<T>(), k == kKernelPairRes || k == kKernelPairMidRes)
+                     : (k == kKernelPair || k == kKernelPairRes) && multi_ == kMultiVol ? prost_hip_fused_iteration3d_x2_chunk_cols(&desc_, dtype_id<T>(), k == kKernelPairRes)
+                     : (k == kKernelPair || k == kKernelPairRes) && multi_ == kMultiMc ? prost_hip_fused_iteration_mc_x2_chunk_cols(&desc_pair_, dtype_id<T>(), k == kKernelPairRes) : 0;
     out.push_back({names[k], sum[k] / cnt[k], cnt[k], launches_[k], iters[k], cols});
   }
   samples_.clear(); ev_used_ = 0; last_end_ = kNoEvent;
