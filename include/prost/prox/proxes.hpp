@@ -45,6 +45,33 @@ class ProxElemDispatch : public ProxSeparableSum<T> {
   std::array<device_vector<T>, 7> d_coeffs_;
 };
 
+/// The spectral family: elem_operation:singular_nx2:* (a function of the two singular values of the n x 2 matrix a group holds,
+/// dim = 2 n), elem_operation:eigen_2x2:* and elem_operation:eigen_3x3:* (a function of the eigenvalues of the symmetrised 2x2 / 3x3
+/// matrix, dim 4 / 9).  Operation and function are run-time ids (PROST_SPECTRAL_*, PROST_FN_* / PROST_FN2D_* of prost_hip.h) of one
+/// kernel family (prost_amd/csrc/kernels_prox_spectral.hip); the arithmetic is prost/prox/elemop/elem_operation_singular_nx2.hpp,
+/// _eigen_2x2.hpp, _eigen_3x3.hpp.  A dimension the operation does not take throws at construction.  The kernel reads the step size
+/// from device memory when asked to (Prox::StepView), so goldstein / boyd keep their device-resident rule on problems that use it.
+template <typename T>
+class ProxSpectral : public ProxSeparableSum<T> {
+ public:
+  ProxSpectral(int op, int fn, size_t index, size_t count, size_t dim, bool interleaved, bool diagsteps, const std::array<std::vector<T>, 7>& coeffs);
+  static const char* OperationName(int op);
+  virtual void Initialize();      // uploads per-group coefficient vectors
+  virtual void Release();
+  virtual size_t gpu_mem_amount() const;
+  virtual bool takes_step_view() const { return true; }
+  int op() const { return op_; }
+  int fn() const { return fn_; }
+
+ protected:
+  virtual void EvalLocal(T*, T*, const T*, const T*, const T*, const T*, T tau, bool invert_tau);
+  virtual void EvalLocalStepView(T*, T*, const T*, const T*, const T*, const T*, const typename Prox<T>::StepView& view, bool invert_tau);
+  void Launch(T* res, const T* arg, const T* tau_diag, T tau, const T* step, const int* stop, bool invert_tau);
+  int op_, fn_;
+  std::array<std::vector<T>, 7> coeffs_;
+  std::array<device_vector<T>, 7> d_coeffs_;
+};
+
 /// prox of the conjugate via Moreau's identity (prox_moreau.cu:98-134)
 template <typename T>
 class ProxMoreau : public Prox<T> {

@@ -286,6 +286,21 @@ int prost_hip_prox_elem_ind_sum_f64(double* res, const double* arg, size_t count
  * 1024-entry per-thread local array, i.e. dim <= 1024; no such limit here). */
 int prost_hip_prox_elem_ind_simplex_f32(float* res, const float* arg, float* work, size_t count, size_t dim, int interleaved, void* stream);
 int prost_hip_prox_elem_ind_simplex_f64(double* res, const double* arg, double* work, size_t count, size_t dim, int interleaved, void* stream);
+/* The spectral proxes (additions; ABI version unchanged): a function of the two singular values of an n x 2 matrix
+ * (include/prost/prox/elemop/elem_operation_singular_nx2.hpp; dim = 2 n, components 0..n-1 = first column) or of the eigenvalues of a
+ * symmetrised column-major 2x2 / 3x3 matrix (elem_operation_eigen_2x2.hpp, dim 4; elem_operation_eigen_3x3.hpp, dim 9).  One group per
+ * lane, the group in registers (singular_nx2 with dim > 12: two passes over HBM), decomposition in fp64 for both data types.
+ * fn: PROST_FN_* (the scalar function applied to every singular value / eigenvalue) or, for singular_nx2 only, PROST_FN2D_*.
+ * The step of a group is tau * tau_diag[first component] (its reciprocal under invert_tau); with step_dev != NULL the scalar is read
+ * from *step_dev on the device and a non-zero *stop_dev makes the kernel return without writing (both NULL or both set; `tau` is then
+ * ignored).  coeff_ptr / coeff_val, the layout rule and the absence of a device sync are those of prost_hip_prox_elem; coefficient
+ * vectors have one value per GROUP.  A bad (op, fn, dim) combination returns an error without launching. */
+enum { PROST_SPECTRAL_SINGULAR_NX2 = 0, PROST_SPECTRAL_EIGEN_2X2 = 1, PROST_SPECTRAL_EIGEN_3X3 = 2 };
+enum { PROST_FN2D_IND_L1_BALL = 100, PROST_FN2D_MOREAU_IND_L1_BALL = 101 };
+int prost_hip_prox_spectral_f32(int op, int fn, float* res, const float* arg, const float* tau_diag, double tau, const float* step_dev, const int* stop_dev,
+                                int invert_tau, size_t count, size_t dim, int interleaved, const float* const* coeff_ptr, const double* coeff_val, void* stream);
+int prost_hip_prox_spectral_f64(int op, int fn, double* res, const double* arg, const double* tau_diag, double tau, const double* step_dev, const int* stop_dev,
+                                int invert_tau, size_t count, size_t dim, int interleaved, const double* const* coeff_ptr, const double* coeff_val, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* PDHG building blocks, generic path (src/backend/backend_pdhg.cu)                            */

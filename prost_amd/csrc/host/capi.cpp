@@ -197,6 +197,21 @@ static Prox<T>* make_elem(int op, int fn, size_t idx, size_t size, bool diagstep
   return new ProxElemDispatch<T>(op, fn, idx, count, dim, interleaved, diagsteps, coeffs);
 }
 
+/// the spectral family (factory.cpp:49-88): same description data as elem_operation:norm2, one coefficient value per GROUP
+template <typename T>
+static Prox<T>* make_spectral(int op, int fn, size_t idx, size_t size, bool diagsteps, const prost_value* data) {
+  const size_t count = (size_t)GetScalarFromCell(data, 0), dim = (size_t)GetScalarFromCell(data, 1);
+  const bool interleaved = GetScalarFromCell(data, 2) > 0.;
+  if (count * dim != size) {
+    std::stringstream ss;
+    ss << ProxSpectral<T>::OperationName(op) << ": size = " << size << " is not count * dim = " << count << " * " << dim << ".";
+    throw Exception(ss.str());
+  }
+  std::array<std::vector<T>, 7> coeffs;
+  get_coefficients<T>(coeffs, cell_at(data, 3), count);
+  return new ProxSpectral<T>(op, fn, idx, count, dim, interleaved, diagsteps, coeffs);
+}
+
 template <typename T>
 std::map<std::string, typename Factory<T>::ProxFactory>& Factory<T>::prox_reg() {
   static std::map<std::string, ProxFactory> reg;
@@ -207,6 +222,20 @@ std::map<std::string, typename Factory<T>::ProxFactory>& Factory<T>::prox_reg() 
       reg[std::string("elem_operation:1d:") + kFunctionNames[fn]] = [fn](size_t idx, size_t size, bool ds, const prost_value* d) { return make_elem<T>(PROST_OP_1D, fn, idx, size, ds, d); };
       reg[std::string("elem_operation:norm2:") + kFunctionNames[fn]] = [fn](size_t idx, size_t size, bool ds, const prost_value* d) { return make_elem<T>(PROST_OP_NORM2, fn, idx, size, ds, d); };
     }
+    for (int fn = 0; fn < PROST_FN_COUNT; fn++) {
+      reg[std::string("elem_operation:eigen_2x2:") + kFunctionNames[fn]] = [fn](size_t idx, size_t size, bool ds, const prost_value* d) { return make_spectral<T>(PROST_SPECTRAL_EIGEN_2X2, fn, idx, size, ds, d); };
+      reg[std::string("elem_operation:eigen_3x3:") + kFunctionNames[fn]] = [fn](size_t idx, size_t size, bool ds, const prost_value* d) { return make_spectral<T>(PROST_SPECTRAL_EIGEN_3X3, fn, idx, size, ds, d); };
+    }
+    // singular_nx2: the ten functions of the reference's table (zero .. huber) under "sum_1d:<fn>".  The builder concatenates its `fun`
+    // argument as it stands (sum_singular_nx2.m:28), so sum_singular_nx2(dim, il, 'ind_leq0', ...) asks for the name WITHOUT "sum_1d:";
+    // the reference does not register that spelling, here it is an alias of the same prox.
+    for (int fn = 0; fn <= PROST_FN_HUBER; fn++) {
+      auto make = [fn](size_t idx, size_t size, bool ds, const prost_value* d) { return make_spectral<T>(PROST_SPECTRAL_SINGULAR_NX2, fn, idx, size, ds, d); };
+      reg[std::string("elem_operation:singular_nx2:sum_1d:") + kFunctionNames[fn]] = make;
+      reg[std::string("elem_operation:singular_nx2:") + kFunctionNames[fn]] = make;
+    }
+    reg["elem_operation:singular_nx2:ind_l1_ball"] = [](size_t idx, size_t size, bool ds, const prost_value* d) { return make_spectral<T>(PROST_SPECTRAL_SINGULAR_NX2, PROST_FN2D_IND_L1_BALL, idx, size, ds, d); };
+    reg["elem_operation:singular_nx2:moreau:ind_l1_ball"] = [](size_t idx, size_t size, bool ds, const prost_value* d) { return make_spectral<T>(PROST_SPECTRAL_SINGULAR_NX2, PROST_FN2D_MOREAU_IND_L1_BALL, idx, size, ds, d); };
     reg["moreau"] = [](size_t, size_t, bool, const prost_value* d) -> Prox<T>* { return new ProxMoreau<T>(Factory<T>::CreateProx(cell_at(d, 0))); };
     reg["zero"] = [](size_t idx, size_t size, bool, const prost_value*) -> Prox<T>* { return new ProxZero<T>(idx, size); };
     reg["elem_operation:ind_sum"] = [](size_t idx, size_t, bool ds, const prost_value* d) -> Prox<T>* {

@@ -136,6 +136,62 @@ bool ProxElemDispatch<T>::supports_op_source() const {
 template class ProxElemDispatch<float>;
 template class ProxElemDispatch<double>;
 
+// ---- spectral: singular_nx2 / eigen_2x2 / eigen_3x3 ----
+template <typename T>
+const char* ProxSpectral<T>::OperationName(int op) {
+  return op == PROST_SPECTRAL_SINGULAR_NX2 ? "singular_nx2" : op == PROST_SPECTRAL_EIGEN_2X2 ? "eigen_2x2" : op == PROST_SPECTRAL_EIGEN_3X3 ? "eigen_3x3" : "spectral";
+}
+template <typename T>
+ProxSpectral<T>::ProxSpectral(int op, int fn, size_t index, size_t count, size_t dim, bool interleaved, bool diagsteps,
+                              const std::array<std::vector<T>, 7>& coeffs)
+    : ProxSeparableSum<T>(index, count, dim, interleaved, diagsteps), op_(op), fn_(fn), coeffs_(coeffs) {
+  std::stringstream ss;
+  if (op == PROST_SPECTRAL_SINGULAR_NX2 && (dim == 0 || dim % 2 != 0)) ss << "singular_nx2: dim = " << dim << ", but a group is an n x 2 matrix: dim has to be even.";
+  else if (op == PROST_SPECTRAL_EIGEN_2X2 && dim != 4) ss << "eigen_2x2: dim = " << dim << ", but a group is a 2 x 2 matrix: dim has to be 4.";
+  else if (op == PROST_SPECTRAL_EIGEN_3X3 && dim != 9) ss << "eigen_3x3: dim = " << dim << ", but a group is a 3 x 3 matrix: dim has to be 9.";
+  else if (op != PROST_SPECTRAL_SINGULAR_NX2 && op != PROST_SPECTRAL_EIGEN_2X2 && op != PROST_SPECTRAL_EIGEN_3X3) ss << "spectral prox: unknown operation id " << op << ".";
+  if (!ss.str().empty()) throw Exception(ss.str());
+  for (int i = 0; i < 7; i++)
+    if (coeffs_[i].empty()) throw Exception(std::string(OperationName(op)) + ": empty coefficient vector passed.");
+}
+template <typename T>
+void ProxSpectral<T>::Initialize() {
+  for (int i = 0; i < 7; i++)
+    if (coeffs_[i].size() > 1) {
+      if (coeffs_[i].size() < this->count_) throw Exception(std::string(OperationName(op_)) + ": size of coefficients should be either 1 or count.");
+      d_coeffs_[i] = coeffs_[i];
+    }
+}
+template <typename T> void ProxSpectral<T>::Release() { for (int i = 0; i < 7; i++) d_coeffs_[i].clear(); }
+template <typename T>
+size_t ProxSpectral<T>::gpu_mem_amount() const {
+  size_t mem = 0;
+  for (int i = 0; i < 7; i++) if (coeffs_[i].size() > 1) mem += this->count_ * sizeof(T);
+  return mem;
+}
+template <typename T>
+void ProxSpectral<T>::Launch(T* res, const T* arg, const T* tau_diag, T tau, const T* step, const int* stop, bool invert_tau) {
+  const T* ptrs[7]; double vals[7];
+  for (int i = 0; i < 7; i++) {
+    if (coeffs_[i].size() > 1) {
+      if (d_coeffs_[i].size() != coeffs_[i].size()) throw Exception(std::string(OperationName(op_)) + ": prox used before Initialize().");
+      ptrs[i] = d_coeffs_[i].data(); vals[i] = 0;
+    } else { ptrs[i] = nullptr; vals[i] = (double)coeffs_[i][0]; }
+  }
+  CheckHip(Api<T>::prox_spectral(op_, fn_, res, arg, tau_diag, (double)tau, step, stop, invert_tau ? 1 : 0, this->count_, this->dim_,
+                                 this->interleaved_ ? 1 : 0, ptrs, vals, CurrentStream()), "prox_spectral");
+}
+template <typename T>
+void ProxSpectral<T>::EvalLocal(T* res, T*, const T* arg, const T*, const T* tau_diag, const T*, T tau, bool invert_tau) {
+  Launch(res, arg, tau_diag, tau, nullptr, nullptr, invert_tau);
+}
+template <typename T>
+void ProxSpectral<T>::EvalLocalStepView(T* res, T*, const T* arg, const T*, const T* tau_diag, const T*, const typename Prox<T>::StepView& view, bool invert_tau) {
+  Launch(res, arg, tau_diag, (T)0, view.step, view.stop, invert_tau);
+}
+template class ProxSpectral<float>;
+template class ProxSpectral<double>;
+
 // ---- Moreau ----
 template <typename T> void ProxMoreau<T>::Initialize() { scaled_arg_.resize(this->size_); conjugate_->Initialize(); }
 template <typename T> void ProxMoreau<T>::Release() { conjugate_->Release(); scaled_arg_.clear(); }

@@ -26,6 +26,29 @@ def sum_norm2(dim, interleaved, fun, a=1, b=0, c=1, d=0, e=0, alpha=0, beta=0):
                                [count // dim, dim, bool(interleaved), coeffs]]
 
 
+def sum_singular_nx2(dim, interleaved, fun, a=1, b=0, c=1, d=0, e=0, alpha=0, beta=0):
+    """sum_singular_nx2.m:1-30: h(sigma_1) + h(sigma_2) of the n x 2 matrix a group of dim = 2n values holds (first column first),
+    h as in sum_1d.  `fun` is appended to the name as it stands, like the .m builder does: 'sum_1d:<fn>' for the ten functions
+    zero .. huber ('<fn>' alone names the same prox here), 'ind_l1_ball' or 'moreau:ind_l1_ball' (radius alpha)."""
+    coeffs = [_coeff(v) for v in (a, b, c, d, e, alpha, beta)]
+    return lambda idx, count: ["elem_operation:singular_nx2:" + fun, idx, count, False,
+                               [count // dim, dim, bool(interleaved), coeffs]]
+
+
+def sum_eigen_2x2(interleaved, fun, a=1, b=0, c=1, d=0, e=0, alpha=0, beta=0):
+    """sum_eigen_2x2.m:1-22: h(lambda_1) + h(lambda_2) of the symmetrised column-major 2 x 2 matrix a group of 4 values holds"""
+    coeffs = [_coeff(v) for v in (a, b, c, d, e, alpha, beta)]
+    return lambda idx, count: ["elem_operation:eigen_2x2:" + fun, idx, count, False,
+                               [count // 4, 4, bool(interleaved), coeffs]]
+
+
+def sum_eigen_3x3(interleaved, fun, a=1, b=0, c=1, d=0, e=0, alpha=0, beta=0):
+    """sum_eigen_3x3.m:1-24: h(lambda_1) + h(lambda_2) + h(lambda_3) of the symmetrised column-major 3 x 3 matrix a group of 9 values holds"""
+    coeffs = [_coeff(v) for v in (a, b, c, d, e, alpha, beta)]
+    return lambda idx, count: ["elem_operation:eigen_3x3:" + fun, idx, count, False,
+                               [count // 9, 9, bool(interleaved), coeffs]]
+
+
 def conjugate(fun):
     def make(idx, count):
         child = fun(idx, count)
