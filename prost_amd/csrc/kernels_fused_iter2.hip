@@ -18,7 +18,22 @@
 // Every stage evaluates exactly the expressions of the single-iteration kernel, so x^(k+2), y^(k+2)
 // are bit-identical to two single launches.  Intermediate iterates are NOT stored: the host only
 // pairs iterations whose intermediate state nobody reads (see BackendPDHG::PerformIterations).
+//
+// Paired march (template parameter PAIR; iter2_grid.hpp).  The warm-up and the run-out exist only because the chunks of a strip do
+// not talk to each other.  The plain launches of the exact fp32 LDS-ring instances run workgroups of two wavefronts on the chunks
+// 2m and 2m+1: both start at the seam s between them, wave 1 marches right over s, s+1, .. with the pipeline above (first step
+// s - 2: A(s) only), wave 0 marches LEFT over s-1, s-2, ...  Going left, the primal stencil (column c-1) reaches ahead of the march
+// and the dual stencil (column c+1) behind it, so the left pipeline is  A(c-1), B(c-1), C(c), D(c)  per step (step_l) -- the same
+// per-pixel lambdas with the same operands.  What a wave needs from across the seam the other wave computes in its first steps:
+//     barrier 1:  x1 at s     right -> left   (left wave's B(s-1), D(s-1))
+//     barrier 2:  y1 (first component) at s-1   left -> right   (right wave's C(s))
+//     barrier 3:  x2 at s     right -> left   (left wave's D(s-1))
+// through three 1-KiB LDS slots, each written once.  Per pair: one warm-up and one run-out instead of two of each.  EVERY wave of a
+// paired workgroup executes exactly three barriers: the left wave always owns a column (steps xb and xb - 1), the right wave either
+// owns one (steps xa - 2 and xa - 1) or -- odd chunk count -- owns nothing and executes the three barriers alone; rec->stop returns
+// before the first barrier and is uniform across the launch.
 #include "fused_common.hpp"
+#include "iter2_grid.hpp"
 #include "reduce.hpp"
 
 #include <type_traits>
@@ -53,8 +68,9 @@ struct Col2 {
 // kernels, src/CMakeLists.txt:12-24), the quotient by the wave-uniform 1 + step as a product with its fp32 reciprocal and
 // pr v / ||v|| as v * min(b * rsq(||v||^2), 1) (v_rsq_f32, 1 ulp) -- no fp64 instruction, no conversion, no range guard.  Results are
 // within a stated tolerance of the exact instances (tests/test_gpu_fmad.py), not bit-identical to them.
-template <class T, int VEC, int GFN, int FFN, int GMASK, int PF, bool FAST, int MODE, bool RAG, bool VART, bool FMAD>
-__global__ void __launch_bounds__(kWave, FAST ? (PF == 0 ? ((MODE & 2) ? 3 : kRingWaves) : (MODE & 2) ? 2 : (PF > 1 || MODE == 1 ? 3 : 4)) : 1)
+// PAIR: two wavefronts per workgroup share the seam between their chunks (header comment: "Paired march"; iter2_grid.hpp)
+template <class T, int VEC, int GFN, int FFN, int GMASK, int PF, bool FAST, int MODE, bool RAG, bool VART, bool FMAD, bool PAIR = false>
+__global__ void __launch_bounds__(PAIR ? 2 * kWave : kWave, FAST ? (PF == 0 ? ((MODE & 2) ? 3 : kRingWaves) : (MODE & 2) ? 2 : (PF > 1 || MODE == 1 ? 3 : 4)) : 1)
     fused_iter2d_x2_kernel(T* __restrict__ x_out, T* __restrict__ y_out,
                                                                 const T* __restrict__ x, const T* __restrict__ y,
                                                                 T* __restrict__ x_mid, T* __restrict__ y_mid,
@@ -68,24 +84,25 @@ __global__ void __launch_bounds__(kWave, FAST ? (PF == 0 ? ((MODE & 2) ? 3 : kRi
   // itself -- 64-bit orderings are vector instructions
   const idx_t nx = (idx_t)a.nx, ny = (idx_t)a.ny;
   const idx_t rx0 = (idx_t)a.rx0, rx1 = a.rx1 > (size_t)0x7fffffff ? (idx_t)0x7fffffff : (idx_t)a.rx1;
-  const int lane = threadIdx.x;
+  static_assert(!PAIR || (PF == 0 && FAST && MODE == 0 && !RAG && !VART && sizeof(T) * VEC == 16), "paired march: plain straight-line LDS-ring instances");
+  const int lane = PAIR ? (int)(threadIdx.x % kWave) : (int)threadIdx.x;
+  // wave of a paired workgroup: 0 marches left over chunk 2m, 1 marches right over chunk 2m+1 (an unpaired wave marches right)
+  const int wv = PAIR ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave)) : 1;
   constexpr int kRowsPerWave = (kWave - 2) * VEC;
-  const unsigned total = gridDim.x, chunks = a.chunks;
-  const unsigned xcd = blockIdx.x % 8u, q = blockIdx.x / 8u;          // XCD-aware tile order (kernels_fused_iter.hip)
-  const unsigned tile = xcd * (total / 8u) + (xcd < total % 8u ? xcd : total % 8u) + q;
+  // XCD-aware tile order (kernels_fused_iter.hip), chunks of one strip consecutive: iter2_grid.hpp
+  const Iter2Span span = iter2_span(blockIdx.x, gridDim.x, (unsigned)wv, a.chunks, a.cols_per_block, (int)a.nx, PAIR);
   // (tried in round 3: vertically adjacent strips as consecutive tiles -- they march over the same columns at the same time, so the
   // rows their halo lanes share and the cache lines their boundaries straddle (a strip is 248 floats = 7.75 lines per column) meet
   // in the XCD's L2.  FETCH_SIZE per launch drops from 177.0 to 155.4 thousand KiB (groups of 2 / 4 strips: 169.6 / 164.9), the
   // total traffic from 564 to 522 MB -- and the launch gets SLOWER, 0.108 against 0.105 ms on the same box: at 5.4 TB/s the kernel
   // is bound by what a wavefront has in flight, not by the bytes; the chunks of one strip stay consecutive.)
-  const unsigned strip = tile / chunks, chunk = tile % chunks;
+  const unsigned strip = span.strip;
   const idx_t row0 = (idx_t)strip * kRowsPerWave + ((idx_t)lane - 1) * VEC;
   const bool active = row0 >= 0 && row0 < ny;
   const bool owner = active && lane > 0 && lane < kWave - 1;
   // RAG: the image height is not a multiple of VEC (fused_common.hpp, ldv_n / stv_n)
   const int nvalid = !RAG ? VEC : (active ? (ny - row0 < (idx_t)VEC ? (int)(ny - row0) : VEC) : 0);   // rows of this lane inside the image
-  const idx_t xa = (idx_t)chunk * a.cols_per_block;
-  const idx_t xb = xa + a.cols_per_block < nx ? xa + a.cols_per_block : nx;
+  const idx_t xa = span.xa, xb = span.xb;
   const size_t N = (size_t)nx * (size_t)ny;
   constexpr bool kUniformG = (GMASK & 0x15) == 0;
   constexpr bool kBMask = FAST && (GMASK & 0x80) != 0;     // bit 7: the per-pixel b carries the mask sentinel (binary coefficient a folded in)
@@ -114,7 +131,11 @@ __global__ void __launch_bounds__(kWave, FAST ? (PF == 0 ? ((MODE & 2) ? 3 : kRi
   // step the batch of column c+3 (NB loads, issued one step ago) may still be in flight, whatever stores lie in between.
   constexpr bool kRing = PF == 0;
   constexpr int NB = 3 + ((GMASK >> 1) & 1);                    // LDS-DMA loads per column: y1, y2, x (, b of prox_g)
-  __shared__ __attribute__((aligned(16))) char ring_mem[kRing ? 2 * 4096 : 16];
+  // PAIR: a ring per wave, then the seam exchange: three columns of VEC values per lane (x^(k+1) and x^(k+2) at the seam column from
+  // the right-marching wave, the first component of y^(k+1) left of the seam from the left-marching wave), 1 KiB each
+  constexpr unsigned kRingBytes = 2 * 4096, kXchBytes = kWave * 16;
+  __shared__ __attribute__((aligned(16))) char ring_mem[kRing ? (PAIR ? 2 * kRingBytes + 3 * kXchBytes : kRingBytes) : 16];
+  char* const ring = ring_mem + (PAIR ? (unsigned)wv * kRingBytes : 0u);
   const T* const y2base = y + N;
   T* const y2out = y_out + N;
   T* const y2mid = kMid ? y_mid + N : nullptr;
@@ -133,21 +154,26 @@ __global__ void __launch_bounds__(kWave, FAST ? (PF == 0 ? ((MODE & 2) ? 3 : kRi
     }
   };
   auto has_col = [&](idx_t k) { return k >= 0 && k < nx && k <= xb + 1; };
-  auto ring_issue = [&](idx_t k) {                                // column k -> slot k & 1
+  // the left-marching wave of a pair reads down to column xa - 1 and, of column xa - 2, y1 alone
+  auto has_col_l = [&](idx_t k) { return k >= 0 && k >= xa - 2 && k < nx; };
+  auto ring_issue = [&](idx_t k, bool y1_only = false) {          // column k -> slot k & 1 (y1_only: a batch of ONE load)
     if (active) {
       const unsigned o = off_of(k);
-      char* slot = ring_mem + (k & 1) * 4096;
+      char* slot = ring + (k & 1) * 4096;
       __builtin_amdgcn_global_load_lds((glb_void_t*)(reinterpret_cast<const char*>(y) + o), (lds_void_t*)(slot), 16, 0, 0);
+      if (y1_only) return;
       __builtin_amdgcn_global_load_lds((glb_void_t*)(reinterpret_cast<const char*>(y2base) + o), (lds_void_t*)(slot + 1024), 16, 0, 0);
       __builtin_amdgcn_global_load_lds((glb_void_t*)(reinterpret_cast<const char*>(x) + o), (lds_void_t*)(slot + 2048), 16, 0, 0);
       if ((GMASK >> 1) & 1) __builtin_amdgcn_global_load_lds((glb_void_t*)(reinterpret_cast<const char*>(a.g_ptr[1]) + o), (lds_void_t*)(slot + 3072), 16, 0, 0);
     }
   };
-  auto ring_fetch = [&](idx_t k, bool next_in_flight, Col& in) {
+  // in_flight: loads of the batch issued after column k's that may still be outstanding (NB, 1 or 0)
+  auto ring_fetch = [&](idx_t k, int in_flight, Col& in) {
     typedef typename VecOf<T>::native V4;
-    if (next_in_flight) { if (NB == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); }
+    if (in_flight == NB) { if (NB == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); }
+    else if (in_flight == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned addr = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)ring_mem) + (unsigned)(k & 1) * 4096u + (unsigned)lane * 16u;
+    const unsigned addr = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)ring) + (unsigned)(k & 1) * 4096u + (unsigned)lane * 16u;
     V4 v0, v1, v2, v3 = {};
     asm volatile("ds_read_b128 %0, %1" : "=v"(v0) : "v"(addr) : "memory");
     asm volatile("ds_read_b128 %0, %1 offset:1024" : "=v"(v1) : "v"(addr) : "memory");
@@ -391,14 +417,22 @@ __global__ void __launch_bounds__(kWave, FAST ? (PF == 0 ? ((MODE & 2) ? 3 : kRi
   if (kRing) {
     // lanes outside the image never receive LDS-DMA data: their slices of both slots read as zeros, like the register version's
     typedef typename VecOf<T>::native V4;
-    V4* rz = reinterpret_cast<V4*>(ring_mem);
+    V4* rz = reinterpret_cast<V4*>(ring);
     const V4 zero = {};
 #pragma unroll
     for (int k = 0; k < 8; k++) rz[k * kWave + lane] = zero;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (active && xa - 2 >= 0) ldv_o<T, VEC, RAG>(y, off_of(xa - 2), in2.y1, nvalid);     // becomes in1.y1 at the top of the first step
-    if (has_col(xa - 1)) ring_issue(xa - 1);
-    ring_issue(xa);
+    if (PAIR && wv == 0) {
+      // left-marching wave: x^k right of the seam (stage B of the seam column), then the first two columns left of it
+      if (active && xb < nx) ldv_o<T, VEC, RAG>(x, off_of(xb), in2.x, nvalid);              // becomes in1.x, then x0, at the top of the first steps
+      ring_issue(xb - 1);
+      if (has_col_l(xb - 2)) ring_issue(xb - 2);
+    } else if (!PAIR || xa < nx) {
+      const idx_t c0 = PAIR ? xa - 2 : xa - 3;                                              // the first step
+      if (active && c0 + 1 >= 0) ldv_o<T, VEC, RAG>(y, off_of(c0 + 1), in2.y1, nvalid);     // becomes in1.y1 at the top of the first step
+      if (has_col(c0 + 2)) ring_issue(c0 + 2);
+      if (has_col(c0 + 3)) ring_issue(c0 + 3);
+    }
   } else if (active) {
     if (xa - 2 >= 0) ldv_o<T, VEC, RAG>(y, off_of(xa - 2), in1.y1, nvalid);
     if (xa - 1 >= 0) load_col(xa - 1, in2);
@@ -407,6 +441,74 @@ __global__ void __launch_bounds__(kWave, FAST ? (PF == 0 ? ((MODE & 2) ? 3 : kRi
   }
   // every lane active and no lane on the first / last image row: the whole strip is interior
   const bool strip_inner = (idx_t)strip * kRowsPerWave - VEC >= 1 && (idx_t)strip * kRowsPerWave + (idx_t)(kWave - 1) * VEC < ny - 1;
+  // seam exchange of a pair (slot 0: x^(k+1) at the seam column, 1: y1^(k+1) left of it, 2: x^(k+2) at the seam column): every
+  // slot is written once, by one wave, before the barrier behind which the other wave reads it
+  auto xch_put = [&](int slot, const T (&v)[VEC]) {
+    T* d = reinterpret_cast<T*>(ring_mem + (PAIR ? 2 * kRingBytes : 0u) + (unsigned)slot * kXchBytes) + lane * VEC;
+#pragma unroll
+    for (int j = 0; j < VEC; j++) d[j] = v[j];
+  };
+  auto xch_get = [&](int slot, T (&v)[VEC]) {
+    const T* d = reinterpret_cast<const T*>(ring_mem + (PAIR ? 2 * kRingBytes : 0u) + (unsigned)slot * kXchBytes) + lane * VEC;
+#pragma unroll
+    for (int j = 0; j < VEC; j++) v[j] = d[j];
+  };
+  // ---- the left-marching wave of a pair ----------------------------------------------------------------------------------
+  // Marching towards smaller columns turns the dependencies round: the primal stencil reaches one column BACK (c - 1, now ahead
+  // of the march, so it waits) and the dual stencil one column FORWARD (c + 1, already behind it).  The pipeline is therefore
+  //     A(c-1): x1 at column c-1   (y^k at c-1 and, its first component, at c-2)
+  //     B(c-1): y1 at column c-1   (x1 at c-1 and c)
+  //     C(c)  : x2 at column c     (y1 at c and c-1)
+  //     D(c)  : y2 at column c     (x2 at c and c+1)
+  // with the loaded columns c-2 (in2), c-1 (in1) and x^k, b of column c (x0, g0).  primal and dual are the lambdas above, called
+  // with the operands of the same pixel as in the right-marching step: the register sets that play "previous" and "next"
+  // column are swapped, no expression changes.  Registers: x1_0 / x1_1 / x1_2 = x1 at c+1 / c / c-1, y1a_0, y1b_0 / y1a_1, y1b_1 =
+  // y1 at c / c-1, x2_0 / x2_1 = x2 at c+1 / c.
+  T x0[VEC] = {}, g0[Col::NG][VEC] = {};
+  auto step_l = [&](auto inner, idx_t c) {
+    constexpr bool I = decltype(inner)::value;
+#pragma unroll
+    for (int j = 0; j < VEC; j++) {
+      x0[j] = in1.x[j];
+#pragma unroll
+      for (int k = 0; k < Col::NG; k++) g0[k][j] = in1.gc[k][j];
+    }
+    in1 = in2;
+    if (has_col_l(c - 2)) ring_fetch(c - 2, has_col_l(c - 3) ? (c - 3 == xa - 2 ? 1 : NB) : 0, in2); else in2 = Col{};
+    if (has_col_l(c - 4)) ring_issue(c - 4, c - 4 == xa - 2);    // into the slot just read
+    const idx_t ca = c - 1;
+    const bool ab = ca >= 0 && ca >= xa - 1 && ca < xb;
+    if (ab) {                                                                                     // stage A
+      const T up = lane_up(in1.y2[VEC - 1]);
+      primal(inner, ca, in1.y1, in1.y2, up, in2.y1, in1.x, in1.gc, p1, x1_2, kt_2);
+    }
+    if constexpr (!I) {
+      if (c == xb) { __syncthreads(); xch_get(0, x1_1); }        // x^(k+1) at the seam column, from the right wave's first step
+    }
+    if (ab) dual(inner, ca, x1_2, x1_1, in1.x, x0, in1.y1, in1.y2, p1, y1a_1, y1b_1, false);     // stage B
+    if constexpr (!I) {
+      if (c == xb) { xch_put(1, y1a_1); __syncthreads(); }       // y1^(k+1) left of the seam, for the right wave's C
+    }
+    if (c < xb) {                                                                                 // stage C
+      const T up = lane_up(y1b_0[VEC - 1]);
+      primal(inner, c, y1a_0, y1b_0, up, y1a_1, x1_1, g0, p2, x2_1, kt_c);
+      if (owner) stv_o<T, VEC, true, RAG>(x_out, off_of(c), x2_1, nvalid);
+    }
+    if constexpr (!I) {
+      if (c == xb - 1) { __syncthreads(); xch_get(2, x2_0); }    // x^(k+2) at the seam column, from the right wave's C
+    }
+    if (c < xb) {                                                                                 // stage D
+      T o1[VEC], o2[VEC];
+      dual(inner, c, x2_1, x2_0, x1_1, x1_0, y1a_0, y1b_0, p2, o1, o2, true);
+      if (owner) { stv_o<T, VEC, true, RAG>(y_out, off_of(c), o1, nvalid); stv_o<T, VEC, true, RAG>(y2out, off_of(c), o2, nvalid); }
+    }
+#pragma unroll
+    for (int j = 0; j < VEC; j++) {
+      x1_0[j] = x1_1[j]; x1_1[j] = x1_2[j];
+      y1a_0[j] = y1a_1[j]; y1b_0[j] = y1b_1[j];
+      x2_0[j] = x2_1[j];
+    }
+  };
   auto step = [&](auto inner, idx_t c) {
     Col pre = {};
     constexpr idx_t kAhead = 2 + PF;
@@ -415,7 +517,7 @@ __global__ void __launch_bounds__(kWave, FAST ? (PF == 0 ? ((MODE & 2) ? 3 : kRi
     const idx_t ca = c + 2, cb = c + 1;
     if (kRing) {
       in1 = in2;
-      if (has_col(ca)) ring_fetch(ca, has_col(ca + 1), in2); else in2 = Col{};
+      if (has_col(ca)) ring_fetch(ca, has_col(ca + 1) ? NB : 0, in2); else in2 = Col{};
       if (has_col(ca + 2)) ring_issue(ca + 2);                 // into the slot just read (the reads above have completed)
     }
     if (ca >= 0 && ca < nx) {                                                                     // stage A
@@ -423,7 +525,13 @@ __global__ void __launch_bounds__(kWave, FAST ? (PF == 0 ? ((MODE & 2) ? 3 : kRi
       const T up = lane_up(in2.y2[VEC - 1]);
       primal(inner, ca, in2.y1, in2.y2, up, in1.y1, in2.x, in2.gc, p1, x1_2, kt_2);
     }
-    if (cb >= 0 && cb >= xa - 1 && cb < nx) dual(inner, cb, x1_1, x1_2, in1.x, in2.x, in1.y1, in1.y2, p1, y1a_1, y1b_1, false);   // stage B
+    if constexpr (PAIR && !decltype(inner)::value) {
+      if (c == xa - 2) { xch_put(0, x1_2); __syncthreads(); }                                     // x^(k+1) at the seam column, for the left wave's B and D
+    }
+    if (cb >= 0 && cb >= (PAIR ? xa : xa - 1) && cb < nx) dual(inner, cb, x1_1, x1_2, in1.x, in2.x, in1.y1, in1.y2, p1, y1a_1, y1b_1, false);   // stage B
+    if constexpr (PAIR && !decltype(inner)::value) {
+      if (c == xa - 1) { __syncthreads(); xch_get(1, y1a_0); }                                    // y1^(k+1) left of the seam, from the left wave's B
+    }
     if (cb >= xa && cb < nx) {                                                                    // stage C
       const T up = lane_up(y1b_1[VEC - 1]);                      // lane 0: no source, its first row is halo
       primal(inner, cb, y1a_1, y1b_1, up, y1a_0, x1_1, in1.gc, p2, x2_1, kt_c);
@@ -464,6 +572,9 @@ __global__ void __launch_bounds__(kWave, FAST ? (PF == 0 ? ((MODE & 2) ? 3 : kRi
         }
       }
     }
+    if constexpr (PAIR && !decltype(inner)::value) {
+      if (c == xa - 1) { xch_put(2, x2_1); __syncthreads(); }                                     // x^(k+2) at the seam column, for the left wave's D
+    }
     if (c >= xa) {                                                                                // stage D
       T o1[VEC], o2[VEC];
       dual(inner, c, x2_0, x2_1, x1_0, x1_1, y1a_0, y1b_0, p2, o1, o2, true);
@@ -489,11 +600,32 @@ __global__ void __launch_bounds__(kWave, FAST ? (PF == 0 ? ((MODE & 2) ? 3 : kRi
       kt_1[j] = kt_2[j];
     }
   };
-  for (idx_t c = xa - 3; c < xb; c++) {
-    // the stencils of this step touch columns c-1 .. c+3 (stage D reads column c+1, stage A column
-    // c+1 .. c+2 and their left neighbours): all strictly inside, all four stages running
-    if (strip_inner && c >= xa && c >= 2 && c + 3 < nx - 1) step(std::true_type(), c);
-    else step(std::false_type(), c);
+  // Every wave of a paired workgroup meets exactly three barriers, whatever its chunk: the left wave at its steps xb and xb - 1
+  // (its chunk always has a column), the right wave at its steps xa - 2 and xa - 1 (xb > xa) or, without a chunk, right here.
+  bool march_right = true;
+  if constexpr (PAIR) {
+    march_right = wv != 0 && xa < nx;
+    if (wv == 0) {
+      // step xb + 1 only loads, step xb runs A and B of the column left of the seam, step xb - 1 is the first full one
+      for (idx_t c = xb + 1; c >= xa; c--) {
+        // stage A reads the columns c-2 .. c-1, stage D column c+1; the seam steps go through the boundary instance
+        if (strip_inner && c <= xb - 2 && c >= 2) step_l(std::true_type(), c);
+        else step_l(std::false_type(), c);
+      }
+    } else if (xa >= nx) {
+      // the chunk right of the seam does not exist (odd chunk count): nothing to compute, and nothing the left wave uses -- what it
+      // reads from the exchange feeds stencil entries right of column nx - 1, which are selected away
+      __syncthreads(); __syncthreads(); __syncthreads();
+    }
+  }
+  if (march_right) {
+    // PAIR: y1^(k+1) at column xa - 1 comes from the left wave, so A(xa - 1) and B(xa - 1) are not recomputed: one warm-up step less
+    for (idx_t c = PAIR ? xa - 2 : xa - 3; c < xb; c++) {
+      // the stencils of this step touch columns c-1 .. c+3 (stage D reads column c+1, stage A column
+      // c+1 .. c+2 and their left neighbours): all strictly inside, all four stages running
+      if (strip_inner && c >= xa && c >= 2 && c + 3 < nx - 1) step(std::true_type(), c);
+      else step(std::false_type(), c);
+    }
   }
   if (kRes) {
     r_pd = wave_sum(r_pd); r_pv = wave_sum(r_pv); r_dd = wave_sum(r_dd); r_dv = wave_sum(r_dv);
@@ -541,9 +673,19 @@ static bool iter2_fmad_shape(const prost_hip_fused_desc* d, int dtype) {
          d->f_coeff_val[1] > 0.0;
 }
 
+// The paired march (two wavefronts per workgroup share the seam of their chunks) exists for the exact fp32 straight-line LDS-ring
+// instances of a plain launch: no residual sums (their per-wave summation order would change), no intermediate iterate, uniform Tau,
+// prox_f* = norm2:ind_leq0 written directly, no merged mask stream (the paired instances of those two shapes spill registers).
+// (PROST_ITER2_NO_PAIR=1 keeps every launch unpaired: A/B measurements)
+static bool iter2_pair_shape(const prost_hip_fused_desc* d, int V, bool res, bool mid) {
+  static const bool off = []() { const char* e = getenv("PROST_ITER2_NO_PAIR"); if (e && atoi(e) != 0) return true; e = getenv("PROST_ITER2_NO_RING"); return e && atoi(e) != 0; }();
+  return !off && V == 4 && !res && !mid && iter2_fast_shape(d) && d->ny % (size_t)V == 0 && !d->var_T && !d->f_moreau && !d->g_b_masked && !iter2_fmad_shape(d, 0);
+}
+
 // chunk length (columns per wavefront) of a launch; `res`: the launch also forms the residual sums
-static int iter2_chunk_cols(const prost_hip_fused_desc* d, int V, bool res, int cols) {
+static int iter2_chunk_cols(const prost_hip_fused_desc* d, int V, bool res, int cols, bool mid = false) {
   const size_t strips = (d->ny + 62 * V - 1) / (62 * V);
+  const bool pair = iter2_pair_shape(d, V, res, mid);
   // resident wavefronts per SIMD of the instance that will run: LDS-ring instances 4 (3 with the residual sums), register-ring
   // instances 3 (2)
   static const bool no_ring = []() { const char* e = getenv("PROST_ITER2_NO_RING"); return e && atoi(e) != 0; }();
@@ -559,12 +701,13 @@ static int iter2_chunk_cols(const prost_hip_fused_desc* d, int V, bool res, int 
     for (int c : {36, 30, 24, 18, 12, 9}) if (strips * ((d->nx + c - 1) / c) * 10 >= slots * 9) { cols = c; break; }
     if (cols == 0) {
       // small images cannot fill the chip: the launch then lasts as long as ONE wave needs for its chunk
-      // (c + 3 pipeline steps), so the shortest chunk that still fits one round wins (256^2: 1 column
-      // 0.009 ms, 6 columns 0.019 ms; 1024^2: 2-3 columns)
+      // (c + 3 pipeline steps, c + 2 in a pair), so the shortest chunk that still fits one round wins (256^2: 1 column
+      // 0.009 ms, 6 columns 0.019 ms; 1024^2: 2-3 columns).  A pair occupies two wave slots even where its second chunk is missing.
       double best = 1e30;
       for (int c : {18, 12, 9, 6, 4, 3, 2, 1}) {
-        const double waves = (double)(strips * ((d->nx + c - 1) / c));
-        const double cost = (c + 3.5) * (waves > (double)slots ? waves / (double)slots : 1.0);
+        const size_t chunks = (d->nx + c - 1) / c;
+        const double waves = (double)(strips * (pair ? 2 * ((chunks + 1) / 2) : chunks));
+        const double cost = (c + (pair ? 2.5 : 3.5)) * (waves > (double)slots ? waves / (double)slots : 1.0);
         if (cost < best) { best = cost; cols = c; }
       }
     }
@@ -585,7 +728,7 @@ static int run_iter2(const prost_hip_fused_desc* d, T* x_out, T* y_out, const T*
   if (out4 && !ws) { set_error("fused double iteration: residuals need the reduction workspace"); return 1; }
   FusedArgs<T> a = make_fused_args<T>(d);
   const size_t strips = (d->ny + 62 * V - 1) / (62 * V);
-  cols = iter2_chunk_cols(d, V, out4 != nullptr, cols);
+  cols = iter2_chunk_cols(d, V, out4 != nullptr, cols, x_mid != nullptr);
   if (out4 && strips * ((d->nx + cols - 1) / cols) > (size_t)kReduceBlocks / 2) { set_error("fused double iteration: grid exceeds the reduction workspace"); return 1; }
   a.cols_per_block = cols;
   a.chunks = (unsigned)((d->nx + cols - 1) / cols);
@@ -612,7 +755,10 @@ static int run_iter2(const prost_hip_fused_desc* d, T* x_out, T* y_out, const T*
                     p[1].ug.den_one && p[1].uf.den_one;
   if (a.fmor && !(fast && mask == 0x2)) { set_error("fused double iteration: a Moreau-wrapped prox_f* runs the straight-line square / abs instance only"); return 1; }
   const bool fmad = fast && iter2_fmad_shape(d, sizeof(T) == 4 ? 0 : 1);
-  dim3 grid((unsigned)(strips * a.chunks)), block(kWave);
+  // paired march: one workgroup of two wavefronts per two chunks (iter2_grid.hpp)
+  const bool pair = fast && !fmad && iter2_pair_shape(d, V, out4 != nullptr, x_mid != nullptr);
+  dim3 grid(iter2_blocks((unsigned)strips, a.chunks, false)), block(kWave);
+  const dim3 grid2(iter2_blocks((unsigned)strips, a.chunks, true)), block2(2 * kWave);
   hipStream_t s = as_stream(stream);
   const int mode = (out4 ? 2 : 0) | (x_mid ? 1 : 0);
   const bool rag = d->ny % V != 0;
@@ -629,6 +775,10 @@ static int run_iter2(const prost_hip_fused_desc* d, T* x_out, T* y_out, const T*
     } else if (fmad) { \
       if constexpr (FASTv && F == PROST_FN_IND_LEQ0 && sizeof(T) == 4) GO5(G, F, M, PFv, FASTv, MODEv, RAGv, false, true); \
       else { set_error("fused double iteration: no tolerance-class instance for this shape"); return 1; } \
+    } else if (pair) { \
+      if constexpr (FASTv && PFv == 0 && MODEv == 0 && !RAGv && sizeof(T) == 4 && F == PROST_FN_IND_LEQ0 && (M & 0x80) == 0) \
+        PH_LAUNCH((fused_iter2d_x2_kernel<T, V, G, F, M, PFv, FASTv, MODEv, RAGv, false, false, true>), grid2, block2, 0, s, x_out, y_out, x, y, x_mid, y_mid, a, p[0], p[1], partial, rec); \
+      else { set_error("fused double iteration: no paired instance for this shape"); return 1; } \
     } else GO5(G, F, M, PFv, FASTv, MODEv, RAGv, false, false); \
   } while (0)
 // straight-line instances of heights that are a multiple of the vector width prefetch through the LDS ring (PF = 0); ragged
