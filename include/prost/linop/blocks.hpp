@@ -1,5 +1,5 @@
 // prost/linop/blocks.hpp -- the in-tree blocks of the hot path
-// (reference: include/prost/linop/block_{gradient2d,gradient3d,sparse,diags,zero}.hpp).
+// (reference: include/prost/linop/block_{gradient2d,gradient3d,sparse,dense,dense_kron_id,id_kron_dense,diags,zero}.hpp).
 #ifndef PROST_LINOP_BLOCKS_HPP_
 #define PROST_LINOP_BLOCKS_HPP_
 #include "prost/device_vector.hpp"
@@ -150,6 +150,56 @@ class BlockKronSparse : public Block<T> {
   std::vector<float> host_val_, host_val_t_;
   device_vector<int32_t> ind_, ind_t_, ptr_, ptr_t_;
   device_vector<float> val_, val_t_;
+};
+
+/// general dense block, K column-major of type T (block_dense.hpp); the products are hand-written kernels instead of gemv calls and
+/// repeat their result bit for bit from call to call
+template <typename T>
+class BlockDense : public Block<T> {
+ public:
+  static BlockDense<T>* CreateFromColFirstData(size_t row, size_t col, size_t nrows, size_t ncols, const std::vector<T>& data);
+  virtual void Initialize();
+  virtual void Release();
+  virtual T row_sum(size_t row, T alpha) const;
+  virtual T col_sum(size_t col, T alpha) const;
+  virtual size_t gpu_mem_amount() const;
+
+ protected:
+  BlockDense(size_t row, size_t col, size_t nrows, size_t ncols) : Block<T>(row, col, nrows, ncols) {}
+  virtual void EvalLocalAdd(T*, T*, const T*, const T*);
+  virtual void EvalAdjointLocalAdd(T*, T*, const T*, const T*);
+  virtual void EvalLocal(T*, T*, const T*, const T*);
+  virtual void EvalAdjointLocal(T*, T*, const T*, const T*);
+  void Product(T* r, const T* x, bool transpose, bool acc);
+  std::vector<T> host_data_;
+  device_vector<T> data_;
+  device_vector<double> workspace_;      ///< partial sums of a split product (prost_hip_dense_gemv_workspace_bytes)
+};
+
+/// kron(K, I_d) (id_first == false, block_dense_kron_id.cu) or kron(I_d, K) (id_first == true, block_id_kron_dense.cu) for a small
+/// dense K, column-major, values of type T (the sparse Kronecker blocks keep float), without forming the product
+template <typename T>
+class BlockKronDense : public Block<T> {
+ public:
+  static BlockKronDense<T>* CreateFromColFirstData(bool id_first, size_t diaglength, size_t row, size_t col, size_t nrows, size_t ncols,
+                                                   const std::vector<T>& data);
+  virtual void Initialize();
+  virtual void Release();
+  virtual T row_sum(size_t row, T alpha) const;
+  virtual T col_sum(size_t col, T alpha) const;
+  virtual size_t gpu_mem_amount() const;
+
+ protected:
+  BlockKronDense(size_t row, size_t col, size_t nrows, size_t ncols) : Block<T>(row, col, nrows, ncols) {}
+  virtual void EvalLocalAdd(T*, T*, const T*, const T*);
+  virtual void EvalAdjointLocalAdd(T*, T*, const T*, const T*);
+  virtual void EvalLocal(T*, T*, const T*, const T*);
+  virtual void EvalAdjointLocal(T*, T*, const T*, const T*);
+  void Product(T* r, const T* x, bool transpose, bool acc);
+  bool id_first_ = false;
+  size_t diaglength_ = 0, mat_nrows_ = 0, mat_ncols_ = 0;
+  std::vector<T> host_data_;
+  device_vector<T> data_;
 };
 
 /// constant-coefficient multi-diagonal block; `identity` maps here (block_diags.hpp, identity.m:11-12)

@@ -168,6 +168,29 @@ int prost_hip_sparse_kron_id_f32(float* res, const float* rhs, size_t diaglength
 int prost_hip_sparse_kron_id_f64(double* res, const double* rhs, size_t diaglength, size_t nrows, const float* val, const int32_t* ptr, const int32_t* ind, void* stream);
 int prost_hip_id_kron_sparse_f32(float* res, const float* rhs, size_t diaglength, size_t nrows, size_t ncols, const float* val, const int32_t* ptr, const int32_t* ind, void* stream);
 int prost_hip_id_kron_sparse_f64(double* res, const double* rhs, size_t diaglength, size_t nrows, size_t ncols, const float* val, const int32_t* ptr, const int32_t* ind, void* stream);
+/* The dense blocks (kernels_linop_dense.hip).  data: the column-major nrows x ncols matrix K on the device, of type T (unlike the
+ * sparse Kronecker blocks above, whose values stay float).  transpose != 0: the adjoint product from the same array.  The _acc forms
+ * add into res, the others overwrite it.  Every output of the two Kronecker products is the reference's own sum: a T that starts at 0,
+ * products added in ascending inner index, then one add into res.
+ * res (+)= kron(K, I_d) rhs: replaces BlockDenseKronIdKernel<T, false / true> (src/linop/block_dense_kron_id.cu:139-146, :169-176) */
+int prost_hip_dense_kron_id_acc_f32(float* res, const float* rhs, size_t diaglength, size_t nrows, size_t ncols, const float* data, int transpose, void* stream);
+int prost_hip_dense_kron_id_acc_f64(double* res, const double* rhs, size_t diaglength, size_t nrows, size_t ncols, const double* data, int transpose, void* stream);
+int prost_hip_dense_kron_id_f32(float* res, const float* rhs, size_t diaglength, size_t nrows, size_t ncols, const float* data, int transpose, void* stream);
+int prost_hip_dense_kron_id_f64(double* res, const double* rhs, size_t diaglength, size_t nrows, size_t ncols, const double* data, int transpose, void* stream);
+/* res (+)= kron(I_d, K) rhs: replaces BlockIdKronDenseKernel<T, false / true> (src/linop/block_id_kron_dense.cu, EvalLocalAdd / EvalAdjointLocalAdd) */
+int prost_hip_id_kron_dense_acc_f32(float* res, const float* rhs, size_t diaglength, size_t nrows, size_t ncols, const float* data, int transpose, void* stream);
+int prost_hip_id_kron_dense_acc_f64(double* res, const double* rhs, size_t diaglength, size_t nrows, size_t ncols, const double* data, int transpose, void* stream);
+int prost_hip_id_kron_dense_f32(float* res, const float* rhs, size_t diaglength, size_t nrows, size_t ncols, const float* data, int transpose, void* stream);
+int prost_hip_id_kron_dense_f64(double* res, const double* rhs, size_t diaglength, size_t nrows, size_t ncols, const double* data, int transpose, void* stream);
+/* res (+)= A rhs / A^T rhs: replaces cublasSgemv / cublasDgemv with alpha = beta = 1 (src/linop/block_dense.cu:92-103, :119-130, :146-157,
+ * :173-184).  No floating-point atomics: split work goes through `workspace` (device memory of at least
+ * prost_hip_dense_gemv_workspace_bytes(nrows, ncols) bytes, 16-byte aligned; may be null where that is 0) and is added in a fixed order,
+ * so a call repeats its result bit for bit. */
+int prost_hip_dense_gemv_acc_f32(float* res, const float* rhs, size_t nrows, size_t ncols, const float* data, int transpose, void* workspace, void* stream);
+int prost_hip_dense_gemv_acc_f64(double* res, const double* rhs, size_t nrows, size_t ncols, const double* data, int transpose, void* workspace, void* stream);
+int prost_hip_dense_gemv_f32(float* res, const float* rhs, size_t nrows, size_t ncols, const float* data, int transpose, void* workspace, void* stream);
+int prost_hip_dense_gemv_f64(double* res, const double* rhs, size_t nrows, size_t ncols, const double* data, int transpose, void* workspace, void* stream);
+size_t prost_hip_dense_gemv_workspace_bytes(size_t nrows, size_t ncols);
 /* x = beta * x (beta == 0 -> zero fill): thrust::fill / transform at linearoperator.cu:140-147 */
 /* x[i] = value (thrust::fill, linearoperator.cu:140-147; also used for preconditioners that are one constant: the
  * gradient blocks' row / column sums are, block_gradient2d.cu:154-163, so nothing is uploaded for them) */

@@ -2,7 +2,7 @@
 
 Each builder returns ``func(row, col, nrows, ncols) -> [[name, row, col, data], [nrows, ncols]]``
 exactly like the MATLAB closures (gradient2d.m:12-14, gradient3d.m:12-14, sparse.m:6-9,
-diags.m:17-20, identity.m:11-12, zero.m:3-4).  Cells are Python lists.
+diags.m:17-20, identity.m:11-12, zero.m:3-4, dense.m, dense_kron_id.m, id_kron_dense.m).  Cells are Python lists.
 """
 import numpy as np
 
@@ -46,6 +46,39 @@ def sparse_kron_id(K, diaglength):
 def id_kron_sparse(K, diaglength):
     """id_kron_sparse.m:1-14: kron(speye(diaglength), K) without forming it"""
     return _kron("id_kron_sparse", K, diaglength)
+
+
+def _full(K):
+    import scipy.sparse as sp
+    K = K.toarray() if sp.issparse(K) else K
+    K = np.array(K, dtype=np.float64, order="F", copy=True)
+    if K.ndim != 2:
+        raise ValueError("K must be a matrix (2-D), got %d-D" % K.ndim)
+    return K
+
+
+def dense(K):
+    """dense.m: a full matrix K, applied without a sparse index structure"""
+    K = _full(K)
+    sz = [K.shape[0], K.shape[1]]
+    return lambda row, col, nrows, ncols: [["dense", row, col, [K]], sz]
+
+
+def _kron_dense(name, K, diaglength):
+    K = _full(K)
+    d = int(diaglength)
+    sz = [K.shape[0] * d, K.shape[1] * d]
+    return lambda row, col, nrows, ncols: [[name, row, col, [K, d]], sz]
+
+
+def dense_kron_id(K, diaglength):
+    """dense_kron_id.m: kron(K, speye(diaglength)) for a full K without forming it"""
+    return _kron_dense("dense_kron_id", K, diaglength)
+
+
+def id_kron_dense(K, diaglength):
+    """id_kron_dense.m: kron(speye(diaglength), K) for a full K without forming it"""
+    return _kron_dense("id_kron_dense", K, diaglength)
 
 
 def diags(nrows, ncols, factors, offsets):

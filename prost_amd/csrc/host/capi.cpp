@@ -339,6 +339,28 @@ std::map<std::string, typename Factory<T>::BlockFactory>& Factory<T>::block_reg(
         std::vector<int32_t> ptr(pm->jc.begin(), pm->jc.end()), ind(pm->ir.begin(), pm->ir.begin() + nnz);
         return BlockKronSparse<T>::CreateFromCSC(id_first != 0, row, col, diaglength, nrows, ncols, nnz, val, ptr, ind);
       };
+    // the dense blocks (factory.cpp:590-601, :694-716): cell 0 is a full matrix, column-major, converted to T.  A sparse cell is refused:
+    // the reference would read its value array as if it were the full matrix.
+    auto dense_data = [](const prost_value* pm) {
+      if (pm->kind == PROST_VALUE_SPARSE || pm->kind != PROST_VALUE_MATRIX) throw Exception("Matrix must be dense!");
+      return std::vector<T>(pm->data.begin(), pm->data.begin() + pm->rows * pm->cols);
+    };
+    reg["dense"] = [dense_data](size_t row, size_t col, const prost_value* d) -> Block<T>* {
+      const prost_value* pm = cell_at(d, 0);
+      return BlockDense<T>::CreateFromColFirstData(row, col, pm->rows, pm->cols, dense_data(pm));
+    };
+    for (int id_first = 0; id_first < 2; id_first++) {
+      const std::string name = id_first ? "id_kron_dense" : "dense_kron_id";
+      reg[name] = [id_first, name, dense_data](size_t row, size_t col, const prost_value* d) -> Block<T>* {
+        const prost_value* pm = cell_at(d, 0);
+        std::vector<T> data = dense_data(pm);
+        if (!d || d->cells.size() < 2 || !d->cells[1] || d->cells[1]->kind != PROST_VALUE_MATRIX || d->cells[1]->data.empty())
+          throw Exception(name + ": diaglength is missing (data cells are {K, diaglength}).");
+        const double diaglength = GetScalarFromCell(d, 1);
+        if (!(diaglength >= 1.0)) throw Exception(name + ": diaglength must be at least 1.");
+        return BlockKronDense<T>::CreateFromColFirstData(id_first != 0, (size_t)diaglength, row, col, pm->rows, pm->cols, data);
+      };
+    }
   }
   return reg;
 }

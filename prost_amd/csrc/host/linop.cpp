@@ -363,6 +363,93 @@ void BlockKronSparse<T>::EvalAdjointLocal(T* r, T*, const T* x, const T*) {
 template class BlockKronSparse<float>;
 template class BlockKronSparse<double>;
 
+// ---- dense blocks ----
+template <typename T>
+BlockDense<T>* BlockDense<T>::CreateFromColFirstData(size_t row, size_t col, size_t nrows, size_t ncols, const std::vector<T>& data) {
+  if (data.size() != nrows * ncols) throw Exception("BlockDense: the data does not have nrows x ncols entries.");
+  BlockDense<T>* b = new BlockDense<T>(row, col, nrows, ncols);
+  b->host_data_ = data;
+  return b;
+}
+template <typename T>
+void BlockDense<T>::Initialize() {
+  data_ = host_data_;
+  workspace_.resize(prost_hip_dense_gemv_workspace_bytes(this->nrows(), this->ncols()) / sizeof(double));
+}
+template <typename T>
+void BlockDense<T>::Release() { data_.clear(); workspace_.clear(); }
+template <typename T>
+T BlockDense<T>::row_sum(size_t row, T alpha) const {                 // block_dense.cu:57-64
+  T sum = 0;
+  for (size_t c = 0; c < this->ncols(); c++) sum += std::pow(std::abs(host_data_[c * this->nrows() + row]), alpha);
+  return sum;
+}
+template <typename T>
+T BlockDense<T>::col_sum(size_t col, T alpha) const {                 // :67-74
+  T sum = 0;
+  for (size_t r = 0; r < this->nrows(); r++) sum += std::pow(std::abs(host_data_[col * this->nrows() + r]), alpha);
+  return sum;
+}
+template <typename T>
+size_t BlockDense<T>::gpu_mem_amount() const {
+  return host_data_.size() * sizeof(T) + prost_hip_dense_gemv_workspace_bytes(this->nrows(), this->ncols());
+}
+template <typename T>
+void BlockDense<T>::Product(T* r, const T* x, bool transpose, bool acc) {
+  if (data_.size() != host_data_.size()) throw Exception("BlockDense used before Initialize().");
+  void* ws = workspace_.empty() ? nullptr : (void*)workspace_.data();
+  if (acc) CheckHip(Api<T>::dense_gemv_acc(r, x, this->nrows(), this->ncols(), data_.data(), transpose ? 1 : 0, ws, CurrentStream()), "dense_gemv_acc");
+  else CheckHip(Api<T>::dense_gemv(r, x, this->nrows(), this->ncols(), data_.data(), transpose ? 1 : 0, ws, CurrentStream()), "dense_gemv");
+}
+template <typename T> void BlockDense<T>::EvalLocalAdd(T* r, T*, const T* x, const T*) { Product(r, x, false, true); }
+template <typename T> void BlockDense<T>::EvalAdjointLocalAdd(T* r, T*, const T* x, const T*) { Product(r, x, true, true); }
+template <typename T> void BlockDense<T>::EvalLocal(T* r, T*, const T* x, const T*) { Product(r, x, false, false); }
+template <typename T> void BlockDense<T>::EvalAdjointLocal(T* r, T*, const T* x, const T*) { Product(r, x, true, false); }
+template class BlockDense<float>;
+template class BlockDense<double>;
+
+template <typename T>
+BlockKronDense<T>* BlockKronDense<T>::CreateFromColFirstData(bool id_first, size_t diaglength, size_t row, size_t col, size_t nrows, size_t ncols,
+                                                             const std::vector<T>& data) {
+  if (data.size() != nrows * ncols) throw Exception("BlockKronDense: the data does not have nrows x ncols entries.");
+  BlockKronDense<T>* b = new BlockKronDense<T>(row, col, nrows * diaglength, ncols * diaglength);
+  b->id_first_ = id_first; b->diaglength_ = diaglength; b->mat_nrows_ = nrows; b->mat_ncols_ = ncols;
+  b->host_data_ = data;
+  return b;
+}
+template <typename T>
+void BlockKronDense<T>::Initialize() { data_ = host_data_; }
+template <typename T>
+void BlockKronDense<T>::Release() { data_.clear(); }
+template <typename T>
+T BlockKronDense<T>::row_sum(size_t row, T alpha) const {             // block_dense_kron_id.cu:100-109, block_id_kron_dense.cu:100-109
+  row = id_first_ ? row % mat_nrows_ : row / diaglength_;
+  T sum = 0;
+  for (size_t i = 0; i < mat_ncols_; i++) sum += std::pow(std::abs(host_data_[i * mat_nrows_ + row]), alpha);
+  return sum;
+}
+template <typename T>
+T BlockKronDense<T>::col_sum(size_t col, T alpha) const {             // :112-121
+  col = id_first_ ? col % mat_ncols_ : col / diaglength_;
+  T sum = 0;
+  for (size_t i = 0; i < mat_nrows_; i++) sum += std::pow(std::abs(host_data_[i + col * mat_nrows_]), alpha);
+  return sum;
+}
+template <typename T>
+size_t BlockKronDense<T>::gpu_mem_amount() const { return host_data_.size() * sizeof(T); }
+template <typename T>
+void BlockKronDense<T>::Product(T* r, const T* x, bool transpose, bool acc) {
+  if (data_.size() != host_data_.size()) throw Exception("BlockKronDense used before Initialize().");
+  auto fn = id_first_ ? (acc ? Api<T>::id_kron_dense_acc : Api<T>::id_kron_dense) : (acc ? Api<T>::dense_kron_id_acc : Api<T>::dense_kron_id);
+  CheckHip(fn(r, x, diaglength_, mat_nrows_, mat_ncols_, data_.data(), transpose ? 1 : 0, CurrentStream()), id_first_ ? "id_kron_dense" : "dense_kron_id");
+}
+template <typename T> void BlockKronDense<T>::EvalLocalAdd(T* r, T*, const T* x, const T*) { Product(r, x, false, true); }
+template <typename T> void BlockKronDense<T>::EvalAdjointLocalAdd(T* r, T*, const T* x, const T*) { Product(r, x, true, true); }
+template <typename T> void BlockKronDense<T>::EvalLocal(T* r, T*, const T* x, const T*) { Product(r, x, false, false); }
+template <typename T> void BlockKronDense<T>::EvalAdjointLocal(T* r, T*, const T* x, const T*) { Product(r, x, true, false); }
+template class BlockKronDense<float>;
+template class BlockKronDense<double>;
+
 // ---- diags block ----
 static bool g_diags_quirk = false;
 template <typename T> void BlockDiags<T>::SetReferenceGridQuirk(bool on) { g_diags_quirk = on; }
