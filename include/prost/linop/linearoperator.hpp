@@ -5,6 +5,8 @@
 #include "prost/device_vector.hpp"
 #include "prost/linop/block.hpp"
 
+struct prost_hip_fused_op;      // include/prost_hip.h
+
 namespace prost {
 
 template <typename T>
@@ -81,6 +83,11 @@ class DualLinearOperator : public LinearOperator<T> {
  protected:
   shared_ptr<LinearOperator<T>> child_;
 };
+
+/// The operator as the table of CSR / gradient blocks of the kernels with the operator inside.  false (`op` is not to be used): a
+/// dualized operator, none or too many blocks, a block that is neither sparse nor a planar gradient, or one `accept_sparse` refuses.
+template <typename T>
+bool DescribeOperatorTable(const LinearOperator<T>& linop, prost_hip_fused_op& op, const std::function<bool(const Block<T>&, const BlockDesc&)>& accept_sparse);
 
 }  // namespace prost
 #endif

@@ -46,17 +46,24 @@ void BackendADMM<T>::Initialize() {
   const size_t records = (size_t)std::max(opts_.cg_max_iter, 0) + 2;
   CheckHip(prost_hip_malloc(&cg_state_, records * prost_hip_cgls_state_bytes()), "malloc");
   CheckHip(prost_hip_memset(cg_state_, 0, records * prost_hip_cgls_state_bytes(), CurrentStream()), "memset");
-  fused_rounds_ = false;
-  pixel_rounds_ = false;
-  fused_op_.nblocks = 0;
   cg_result_index_ = 0;
-  if (opts_.device_cg && opts_.fused_rounds && !opts_.cg_graph) DescribeOperator();
+  cg_epoch_ = 0;
+  cg_iters_valid_ = true;
+  // the mode: the options say what is allowed, the operator what is possible (CSR blocks: the short-row kind the one-thread-per-row
+  // product is meant for, up to 6 entries per row and per column).  Below it only what the mode needs is allocated.
+  const auto short_rows = [](const Block<T>& b, const BlockDesc& bd) { return (double)bd.nnz <= 6.0 * (double)b.nrows() && (double)bd.nnz <= 6.0 * (double)b.ncols(); };
+  if (!opts_.device_cg) cg_mode_ = kCgHost;
+  else if (opts_.cg_graph) cg_mode_ = kCgGraph;
+  else if (!opts_.fused_rounds || !DescribeOperatorTable<T>(*this->problem_->linop(), fused_op_, short_rows) || prost_hip_fused_op_supported(&fused_op_, m, n) != 1) cg_mode_ = kCgStaged;
+  else cg_mode_ = opts_.pixel_rounds && DescribePixelOperator() ? kCgPixel : kCgFused4;
+  if (cg_mode_ == kCgPixel) {
+    cg_p_alt_.resize(n); cg_r_alt_.resize(m);
+    pixel_op_.p_alt = cg_p_alt_.data(); pixel_op_.r_alt = cg_r_alt_.data();
+  }
   CheckHip(prost_hip_malloc(&cg_workspace_, prost_hip_cgls_workspace_bytes()), "malloc");
   CheckHip(prost_hip_host_alloc((void**)&cg_done_host_, sizeof(int)), "host_alloc");
   *cg_done_host_ = 0;
-  cg_epoch_ = 0;
-  cg_iters_valid_ = true;
-  if (opts_.cg_graph) {
+  if (cg_mode_ == kCgGraph) {
     CheckHip(prost_hip_stream_create(&cg_stream_), "stream_create");
     CheckHip(prost_hip_event_create(&cg_ev_[0]), "event_create");
     CheckHip(prost_hip_event_create(&cg_ev_[1]), "event_create");
@@ -160,201 +167,163 @@ int BackendADMM<T>::Cgls(const device_vector<T>& b, device_vector<T>& x, double 
   return flag;
 }
 
-
-/// The operator as a table of CSR / gradient blocks for prost_hip_cgls_round_*: every block must describe itself as one of
-/// those (plugin blocks, diags, Kronecker blocks, label_first gradients and dualized operators do not), CSR blocks must be the
-/// short-row kind the one-thread-per-row product is meant for (what prost_hip_csr_spmv itself picks up to 6 entries per row).
+/// v[begin .. end) holds ONE value
 template <typename T>
-void BackendADMM<T>::DescribeOperator() {
-  auto linop = this->problem_->linop();
-  if (dynamic_cast<DualLinearOperator<T>*>(linop.get())) return;
-  const auto& blocks = linop->blocks();
-  if (blocks.empty() || blocks.size() > (size_t)PROST_HIP_OP_MAX_BLOCKS) return;
-  prost_hip_fused_op op;
-  op.nblocks = 0;
-  for (const auto& b : blocks) {
-    BlockDesc bd;
-    if (!b->describe(bd)) return;
-    prost_hip_op_block& o = op.block[op.nblocks++];
-    o.row = b->row(); o.col = b->col(); o.nrows = b->nrows(); o.ncols = b->ncols();
-    o.nx = o.ny = o.L = 0;
-    o.val = o.val_t = nullptr; o.ptr = o.ind = o.ptr_t = o.ind_t = nullptr;
-    o.ids = o.ids_t = nullptr; o.pptr = o.rel = o.pptr_t = o.rel_t = nullptr; o.pval = o.pval_t = nullptr; o.anchor = o.anchor_t = nullptr;
-    if (bd.kind == BlockDesc::kSparse) {
-      if ((double)bd.nnz > 6.0 * (double)b->nrows() || (double)bd.nnz > 6.0 * (double)b->ncols()) return;
-      o.kind = PROST_OP_CSR;
-      o.val = bd.val; o.ptr = bd.ptr; o.ind = bd.ind; o.val_t = bd.val_t; o.ptr_t = bd.ptr_t; o.ind_t = bd.ind_t;
-      o.ids = bd.ids; o.pptr = bd.pptr; o.rel = bd.rel; o.pval = bd.pval; o.ids_t = bd.ids_t; o.pptr_t = bd.pptr_t; o.rel_t = bd.rel_t; o.pval_t = bd.pval_t; o.anchor = bd.anchor; o.anchor_t = bd.anchor_t;
-    } else if ((bd.kind == BlockDesc::kGradient2D || bd.kind == BlockDesc::kGradient3D) && !bd.label_first) {
-      o.kind = bd.kind == BlockDesc::kGradient2D ? PROST_OP_GRAD2D : PROST_OP_GRAD3D;
-      o.nx = bd.nx; o.ny = bd.ny; o.L = bd.L;
-    } else {
-      return;
-    }
-  }
-  if (prost_hip_fused_op_supported(&op, this->problem_->nrows(), this->problem_->ncols()) != 1) return;
-  fused_op_ = op;
-  fused_rounds_ = true;
-  // K = [D ; gradient2d(nx, ny, L)] (either order) with D coupling the L channels of one pixel, or the gradient alone: the CG rounds
-  // of two launches (prost_hip_cgls_pixel_round_*)
-  if (!opts_.pixel_rounds || blocks.size() > 2) return;
+static bool ConstantOn(const std::vector<T>& v, size_t begin, size_t end) {
+  std::atomic<bool> same(true);
+  ParallelFor(end - begin, [&](size_t lo, size_t hi) { for (size_t i = lo; i < hi; i++) if (v[begin + i] != v[begin]) { same.store(false); return; } });
+  return same.load();
+}
+
+/// K = [D ; gradient2d(nx, ny, L)] (either order), D coupling the channels of one pixel or any CSR block with one row per pixel, or the
+/// gradient alone: the two-launch rounds (prost_hip_cgls_pixel_round_*).  Reads fused_op_; fills pixel_op_ but for p_alt / r_alt.
+template <typename T>
+bool BackendADMM<T>::DescribePixelOperator() {
+  const auto& blocks = this->problem_->linop()->blocks();
+  if (blocks.size() > 2) return false;
   const prost_hip_op_block* grad = nullptr; const prost_hip_op_block* dblk = nullptr;
   size_t planes = 0;
   for (size_t i = 0; i < blocks.size(); i++) {
+    const prost_hip_op_block& o = fused_op_.block[i];
     BlockDesc bd;
     blocks[i]->describe(bd);
-    if (op.block[i].kind == PROST_OP_GRAD2D && !grad) grad = &op.block[i];
-    else if (op.block[i].kind == PROST_OP_CSR && bd.pointwise_planes > 0 && bd.val && !dblk) { dblk = &op.block[i]; planes = bd.pointwise_planes; }
-    // round 6: any CSR block with one row per pixel (a warp matrix that gathers at displaced pixels) -- both directions as plain CSR arrays
-    else if (op.block[i].kind == PROST_OP_CSR && bd.val && bd.ptr && bd.ind && bd.val_t && bd.ptr_t && bd.ind_t && !dblk) { dblk = &op.block[i]; planes = 0; }
-    else return;
+    if (o.kind == PROST_OP_GRAD2D && !grad) grad = &o;
+    else if (o.kind == PROST_OP_CSR && bd.pointwise_planes > 0 && bd.val && !dblk) { dblk = &o; planes = bd.pointwise_planes; }
+    else if (o.kind == PROST_OP_CSR && bd.val && bd.ptr && bd.ind && bd.val_t && bd.ptr_t && bd.ind_t && !dblk) { dblk = &o; planes = 0; }     // both directions as plain CSR arrays
+    else return false;
   }
-  if (!grad || grad->col != 0 || grad->L < 1 || grad->L > 3) return;
+  if (!grad || grad->col != 0 || grad->L < 1 || grad->L > 3) return false;
   prost_hip_pixel_op po;
   std::memset(&po, 0, sizeof(po));
   po.nx = grad->nx; po.ny = grad->ny; po.L = (int)grad->L; po.has_d = dblk ? 1 : 0;
   po.d_first = dblk && dblk < grad ? 1 : 0;                 // position in the block LIST (the order K^T t is accumulated in)
   po.g_row = grad->row; po.d_row = dblk ? dblk->row : 0; po.w = dblk ? dblk->val : nullptr;
-  po.p_alt = po.r_alt = nullptr;
-  if (dblk && (dblk->col != 0 || dblk->nrows != grad->nx * grad->ny)) return;
+  if (dblk && (dblk->col != 0 || dblk->nrows != grad->nx * grad->ny)) return false;
   if (dblk && planes == 0) {
-    if (dblk->ncols != grad->L * grad->nx * grad->ny) return;
+    if (dblk->ncols != grad->L * grad->nx * grad->ny) return false;
     po.d_csr = 1; po.w = nullptr;
     po.d_val = dblk->val; po.d_ptr = dblk->ptr; po.d_ind = dblk->ind; po.dt_val = dblk->val_t; po.dt_ptr = dblk->ptr_t; po.dt_ind = dblk->ind_t;
   } else if (dblk && planes != grad->L) {
-    return;
+    return false;
   }
   // Sigma must be ONE value on the gradient rows (it is for the alpha-preconditioners: every row of a gradient block sums to 2,
   // block_gradient2d.cu:154-158; user-supplied scaling vectors may differ): the rounds read it as a scalar
-  {
-    const std::vector<T>& sl = this->problem_->scaling_left_host();
-    const size_t g0 = (size_t)grad->row, g1 = g0 + (size_t)grad->nrows;
-    if (sl.size() < g1) return;
-    const T v0 = sl[g0];
-    std::atomic<bool> same(true);
-    ParallelFor(g1 - g0, [&](size_t lo, size_t hi) { for (size_t i = lo; i < hi; i++) if (sl[g0 + i] != v0) { same.store(false); return; } });
-    if (!same.load()) return;
-    po.sigma_grad = (double)v0;
-  }
-  if (prost_hip_pixel_op_supported(&po, this->problem_->nrows(), this->problem_->ncols(), sizeof(T) == 4 ? 0 : 1) != 1) return;
-  cg_p_alt_.resize(this->problem_->ncols());
-  cg_r_alt_.resize(this->problem_->nrows());
-  po.p_alt = cg_p_alt_.data(); po.r_alt = cg_r_alt_.data();
+  const std::vector<T>& sl = this->problem_->scaling_left_host();
+  const size_t g0 = (size_t)grad->row, g1 = g0 + (size_t)grad->nrows;
+  if (sl.size() < g1 || !ConstantOn(sl, g0, g1)) return false;
+  po.sigma_grad = (double)sl[g0];
+  if (prost_hip_pixel_op_supported(&po, this->problem_->nrows(), this->problem_->ncols(), sizeof(T) == 4 ? 0 : 1) != 1) return false;
   pixel_op_ = po;
-  pixel_rounds_ = true;
+  return true;
 }
 
-/// The same solve with the CG scalars resident on the device (prost_hip_cgls_stage_*): no host round
-/// trip per iteration.  All maxit rounds are queued unless the pinned stop word shows that the device
-/// already met the stopping test; rounds queued after that point return immediately on the device.
+/// One CG round on the current stream, by mode; `events` (or null): the group of events the round's kernels stamp.
 template <typename T>
-void BackendADMM<T>::CglsDevice(const device_vector<T>& b, device_vector<T>& x, double shift, double tol, int maxit,
-                                device_vector<T>& p, device_vector<T>& q, device_vector<T>& r, device_vector<T>& s) {
+void BackendADMM<T>::LaunchRound(const prost_hip_cgls_desc& d, int k, void* const* events) {
   void* st = CurrentStream();
+  if (cg_mode_ == kCgPixel) {
+    if (events) CheckHip(Api<T>::cgls_pixel_round_timed(&d, &pixel_op_, k, events, st), "cgls_pixel_round");
+    else CheckHip(Api<T>::cgls_pixel_round(&d, &pixel_op_, k, st), "cgls_pixel_round");
+  } else if (cg_mode_ == kCgFused4) {
+    if (events) CheckHip(Api<T>::cgls_round_timed(&d, &fused_op_, k, events, st), "cgls_round");
+    else CheckHip(Api<T>::cgls_round(&d, &fused_op_, k, st), "cgls_round");
+  } else {
+    LinearOperator<T>* K = this->problem_->linop().get();
+    K->Eval(z_half_, temp3_, 0);
+    for (int which : {PROST_CGLS_STEP_Q, PROST_CGLS_STEP_XR}) CheckHip(Api<T>::cgls_stage(which, &d, st), "cgls_stage");
+    K->EvalAdjoint(x_dual_, temp3_, 1);
+    for (int which : {PROST_CGLS_STEP_S, PROST_CGLS_STEP_P}) CheckHip(Api<T>::cgls_stage(which, &d, st), "cgls_stage");
+  }
+}
+
+/// kCgGraph: the rounds take no per-solve argument (tolerance and epoch sit in the device record, the vectors are members), so they are
+/// captured ONCE and replayed with one host call per solve.  Opt-in: the replay measured 0.11 ms slower per solve.
+template <typename T>
+void BackendADMM<T>::ReplayRounds(const prost_hip_cgls_desc& d, int maxit) {
+  void* st = CurrentStream();
+  if (!cg_graph_) {
+    SetCurrentStream(cg_stream_);
+    try {
+      CheckHip(prost_hip_stream_begin_capture(cg_stream_), "begin_capture");
+      for (int k = 0; k < maxit; ++k) LaunchRound(d, k, nullptr);
+      CheckHip(prost_hip_stream_end_capture(cg_stream_, &cg_graph_), "end_capture");
+    } catch (...) { SetCurrentStream(st); throw; }
+    SetCurrentStream(st);
+  }
+  CheckHip(prost_hip_event_record(cg_ev_[0], st), "event_record");
+  CheckHip(prost_hip_stream_wait_event(cg_stream_, cg_ev_[0]), "stream_wait_event");
+  CheckHip(prost_hip_graph_launch(cg_graph_, cg_stream_), "graph_launch");
+  CheckHip(prost_hip_event_record(cg_ev_[1], cg_stream_), "event_record");
+  CheckHip(prost_hip_stream_wait_event(st, cg_ev_[1]), "stream_wait_event");
+}
+
+/// the next group of the event pool (grown on demand), for the sampled round of a sampled solve
+template <typename T>
+void* const* BackendADMM<T>::TakeSampleEvents() {
+  while (ev_.size() < ev_used_ + kEventsPerSample) { void* e; CheckHip(prost_hip_event_create(&e), "event_create"); ev_.push_back(e); }
+  ev_used_ += kEventsPerSample;
+  return ev_.data() + ev_used_ - kEventsPerSample;
+}
+
+/// The solve with the CG scalars resident on the device.  All maxit rounds are queued unless the pinned stop word shows that the
+/// device already met the stopping test; rounds queued after that point return at once on the device.
+template <typename T>
+void BackendADMM<T>::CglsDevice(double tol) {
+  void* st = CurrentStream();
+  const int maxit = opts_.cg_max_iter;
   prost_hip_cgls_desc d;
   d.state = cg_state_; d.workspace = cg_workspace_;
-  d.b = b.data(); d.x = x.data(); d.p = p.data(); d.q = q.data(); d.r = r.data(); d.s = s.data(); d.t = temp3_.data();
+  d.b = z_dual_.data(); d.x = x_proj_.data(); d.p = x_half_.data(); d.q = z_half_.data(); d.r = z_proj_.data(); d.s = x_dual_.data(); d.t = temp3_.data();
   d.sigma = this->problem_->scaling_left().data(); d.tau = this->problem_->scaling_right().data();
   d.m = this->problem_->nrows(); d.n = this->problem_->ncols();
-  d.shift = shift; d.tol = tol;
+  d.shift = 1; d.tol = tol;
   d.host_done = cg_done_host_; d.epoch = ++cg_epoch_;
-  auto stage = [&](int which) { CheckHip(Api<T>::cgls_stage(which, &d, st), "cgls_stage"); };
-  LinearOperator<T>* K = this->problem_->linop().get();
-  auto round = [&]() {
-    K->Eval(q, temp3_, 0);
-    stage(PROST_CGLS_STEP_Q);
-    stage(PROST_CGLS_STEP_XR);
-    K->EvalAdjoint(s, temp3_, 1);
-    stage(PROST_CGLS_STEP_S);
-    stage(PROST_CGLS_STEP_P);
-  };
-  cg_result_index_ = 0;
-  if (fused_rounds_) {
-    // the operator inside the kernels: three launches + two scalar kernels to start, four launches per round; record j + 1
-    // is written by round j
+  // the start: record 0
+  if (OperatorInside()) {
     CheckHip(Api<T>::cgls_init_fused(&d, &fused_op_, st), "cgls_init_fused");
-    int queued = 0;
-    // kernel timing: the second round of one solve in `sample_every_` is bracketed kernel by kernel (at most 512 samples)
-    const bool sample = this->time_kernels_ && (solves_++ % (size_t)this->sample_every_) == 0 && ev_used_ + 8 <= 8 * 512;
-    for (int k = 0; k < maxit; ++k) {
-      if (*static_cast<volatile int*>(cg_done_host_) == d.epoch) break;
-      if (sample && k == (maxit > 1 ? 1 : 0)) {
-        while (ev_.size() < ev_used_ + 8) { void* e; CheckHip(prost_hip_event_create(&e), "event_create"); ev_.push_back(e); }
-        if (pixel_rounds_) {
-          // two launches per round: events 0-3 of the group of eight are used, 4-7 stay unrecorded (KernelTimes reads two kernels)
-          CheckHip(Api<T>::cgls_pixel_round_timed(&d, &pixel_op_, k, ev_.data() + ev_used_, st), "cgls_pixel_round");
-        } else {
-          CheckHip(Api<T>::cgls_round_timed(&d, &fused_op_, k, ev_.data() + ev_used_, st), "cgls_round");
-        }
-        ev_used_ += 8;
-      } else if (pixel_rounds_) {
-        CheckHip(Api<T>::cgls_pixel_round(&d, &pixel_op_, k, st), "cgls_pixel_round");
-      } else {
-        CheckHip(Api<T>::cgls_round(&d, &fused_op_, k, st), "cgls_round");
-      }
-      queued++;
-    }
-    // the last queued round's beta / stopping test -> record `queued` (the four-launch rounds write it themselves)
-    if (pixel_rounds_ && queued > 0) CheckHip(Api<T>::cgls_pixel_close(&d, &pixel_op_, queued - 1, st), "cgls_pixel_close");
-    if (this->time_kernels_) rounds_launched_ += (size_t)queued;
-    cg_result_index_ = queued;
-    cg_iters_valid_ = false;
-    return;
-  }
-  stage(PROST_CGLS_INIT_X);
-  stage(PROST_CGLS_INIT_R);
-  K->Eval(r, temp3_, 1);
-  stage(PROST_CGLS_INIT_R2);
-  K->EvalAdjoint(s, temp3_, 1);
-  stage(PROST_CGLS_INIT_S);
-  if (opts_.cg_graph && maxit > 0) {
-    // The maxit rounds take no per-solve argument (tolerance and epoch sit in the device record, the vectors are
-    // members), so they can be captured ONCE into a HIP graph and replayed with one host call per solve.
-    // Opt-in: on ROCm 7.2 / MI355X the replay of the 80-node graph measured 0.11 ms slower per solve than the direct
-    // launches at every size tried (256^2: 0.57 vs 0.45 ms per outer iteration), see DESIGN.md.
-    if (!cg_graph_) {
-      void* prev = CurrentStream();
-      SetCurrentStream(cg_stream_);
-      st = cg_stream_;
-      try {
-        CheckHip(prost_hip_stream_begin_capture(cg_stream_), "begin_capture");
-        for (int k = 0; k < maxit; ++k) round();
-        CheckHip(prost_hip_stream_end_capture(cg_stream_, &cg_graph_), "end_capture");
-      } catch (...) { SetCurrentStream(prev); throw; }
-      SetCurrentStream(prev);
-      st = prev;
-    }
-    CheckHip(prost_hip_event_record(cg_ev_[0], st), "event_record");
-    CheckHip(prost_hip_stream_wait_event(cg_stream_, cg_ev_[0]), "stream_wait_event");
-    CheckHip(prost_hip_graph_launch(cg_graph_, cg_stream_), "graph_launch");
-    CheckHip(prost_hip_event_record(cg_ev_[1], cg_stream_), "event_record");
-    CheckHip(prost_hip_stream_wait_event(st, cg_ev_[1]), "stream_wait_event");
   } else {
-    for (int k = 0; k < maxit; ++k) {
+    LinearOperator<T>* K = this->problem_->linop().get();
+    for (int which : {PROST_CGLS_INIT_X, PROST_CGLS_INIT_R}) CheckHip(Api<T>::cgls_stage(which, &d, st), "cgls_stage");
+    K->Eval(z_proj_, temp3_, 1);
+    CheckHip(Api<T>::cgls_stage(PROST_CGLS_INIT_R2, &d, st), "cgls_stage");
+    K->EvalAdjoint(x_dual_, temp3_, 1);
+    CheckHip(Api<T>::cgls_stage(PROST_CGLS_INIT_S, &d, st), "cgls_stage");
+  }
+  // the rounds.  Kernel timing: ONE round of one solve in `sample_every_` is stamped, the second (later ones may return at once)
+  int queued = 0;
+  if (cg_mode_ == kCgGraph) {
+    if (maxit > 0) ReplayRounds(d, maxit);
+  } else {
+    const bool sample = OperatorInside() && this->time_kernels_ && (solves_++ % (size_t)this->sample_every_) == 0 && ev_used_ + kEventsPerSample <= kEventsPerSample * kMaxSamples;
+    const int sampled_round = maxit > 1 ? 1 : 0;
+    for (; queued < maxit; ++queued) {
       if (*static_cast<volatile int*>(cg_done_host_) == d.epoch) break;
-      round();
+      LaunchRound(d, queued, sample && queued == sampled_round ? TakeSampleEvents() : nullptr);
     }
   }
+  // the result: record 0 (staged rounds) or record `queued` (the pixel rounds write it with one more launch)
+  if (cg_mode_ == kCgPixel && queued > 0) CheckHip(Api<T>::cgls_pixel_close(&d, &pixel_op_, queued - 1, st), "cgls_pixel_close");
+  if (OperatorInside() && this->time_kernels_) rounds_launched_ += (size_t)queued;
+  cg_result_index_ = OperatorInside() ? queued : 0;
   cg_iters_valid_ = false;
 }
 
-/// mean duration of the four kernels of a CG round over the rounds sampled since the last call (rounds that ran after the
-/// stopping test fired return at once and would show up as ~2 us launches: the sampled round is the second of a solve)
+/// mean duration of the kernels of a CG round over the rounds sampled since the last call
 template <typename T>
 void BackendADMM<T>::KernelTimes(std::vector<typename Backend<T>::KernelTime>& out) {
   out.clear();
   if (ev_used_ == 0) return;
-  CheckHip(prost_hip_event_synchronize(ev_[pixel_rounds_ ? ev_used_ - 5 : ev_used_ - 1]), "event_synchronize");      // the last RECORDED event of the last group
   static const char* const names4[4] = {"op_stage_kernel<EpiFwdQ>", "cg_step_xr2_kernel", "op_stage_kernel<EpiAdjS>", "cg_step_p2_kernel"};
   static const char* const names2[4] = {"cg_pixel_pq_kernel", "cg_pixel_xrs_kernel", "", ""};
-  const char* const* names = pixel_rounds_ ? names2 : names4;
-  const int kernels = pixel_rounds_ ? 2 : 4;
+  const char* const* names = cg_mode_ == kCgPixel ? names2 : names4;
+  const int kernels = KernelsPerRound();
+  CheckHip(prost_hip_event_synchronize(ev_[ev_used_ - kEventsPerSample + 2 * kernels - 1]), "event_synchronize");      // the last RECORDED event of the last group
   double sum[4] = {0, 0, 0, 0};
-  const size_t samples = ev_used_ / 8;
+  const size_t samples = ev_used_ / kEventsPerSample;
   for (size_t s = 0; s < samples; s++)
     for (int k = 0; k < kernels; k++) {                       // the kernel's own begin / end stamps (hipExtLaunchKernel): no marker in between
       float ms = 0;
-      CheckHip(prost_hip_event_elapsed_ms(ev_[8 * s + 2 * k], ev_[8 * s + 2 * k + 1], &ms), "event_elapsed");
+      CheckHip(prost_hip_event_elapsed_ms(ev_[kEventsPerSample * s + 2 * k], ev_[kEventsPerSample * s + 2 * k + 1], &ms), "event_elapsed");
       sum[k] += ms;
     }
   for (int k = 0; k < kernels; k++) out.push_back({names[k], sum[k] / (double)samples, samples, rounds_launched_, 0, 0});
@@ -381,7 +350,12 @@ void BackendADMM<T>::GetDual(device_vector<T>& out, const device_vector<T>& half
 
 template <typename T>
 void BackendADMM<T>::PerformIteration() {
-  if (opts_.device_cg) PerformIterationFused(); else PerformIterationUnfused();
+  if (cg_mode_ == kCgHost) PerformIterationUnfused(); else PerformIterationFused();
+}
+
+template <typename T>
+double BackendADMM<T>::CgTolerance() const {                                                           // :408-410
+  return std::max(opts_.cg_tol_min / std::pow((double)static_cast<T>(iteration_ + 1), opts_.cg_tol_pow), opts_.cg_tol_max);
 }
 
 /// residual bookkeeping shared by both paths: all-reduce over ranks, rho adaptation (:618-663)
@@ -419,6 +393,29 @@ void BackendADMM<T>::FinishResiduals(double primal_residual, double primal_var_n
   CheckHip(prost_hip_check_last_error(), "ADMM iteration");
 }
 
+/// PROST_ADMM_FUSED_PRE / _POST / _RES: one entry point with the operator inside, or the stages with LinearOperator::Eval between them
+template <typename T>
+void BackendADMM<T>::OuterStage(int which, const prost_hip_admm_desc& d) {
+  void* st = CurrentStream();
+  if (OperatorInside()) { CheckHip(Api<T>::admm_fused_stage(which, &d, &fused_op_, st), "admm_fused_stage"); return; }
+  auto stage = [&](int s) { CheckHip(Api<T>::admm_stage(s, &d, st), "admm_stage"); };
+  LinearOperator<T>* K = this->problem_->linop().get();
+  if (which == PROST_ADMM_FUSED_PRE) {
+    stage(PROST_ADMM_STAGE_PRE_X); stage(PROST_ADMM_STAGE_PRE_Z);
+    K->Eval(z_dual_, temp3_, 1);
+    stage(PROST_ADMM_STAGE_PRE_Z2);
+  } else if (which == PROST_ADMM_FUSED_POST) {
+    stage(PROST_ADMM_STAGE_POST_X);
+    K->Eval(z_proj_, x_proj_);
+    stage(PROST_ADMM_STAGE_POST_XZ);
+  } else {
+    K->Eval(tmp_m_, x_half_);
+    stage(PROST_ADMM_STAGE_RES_Z);
+    K->EvalAdjoint(tmp_n_, tmp_m_);
+    stage(PROST_ADMM_STAGE_RES_X);                       // the fold writes the four norms to pinned host memory
+  }
+}
+
 /// The iteration on the fused passes of prost_hip_admm_stage_* with the device-resident CGLS: the same
 /// per-element expressions as PerformIterationUnfused, 7 passes + 2 prox + 5 operator applications
 /// outside the CG solve instead of ~45 launches, and ONE host synchronisation (the four residual norms).
@@ -427,8 +424,6 @@ void BackendADMM<T>::PerformIterationFused() {
   const size_t m = this->problem_->nrows(), n = this->problem_->ncols();
   const device_vector<T>& Sl = this->problem_->scaling_left();
   const device_vector<T>& Tr = this->problem_->scaling_right();
-  void* st = CurrentStream();
-  LinearOperator<T>* K = this->problem_->linop().get();
   prost_hip_admm_desc d;
   d.workspace = cg_workspace_;
   d.x_half = x_half_.data(); d.x_proj = x_proj_.data(); d.x_dual = x_dual_.data();
@@ -439,30 +434,13 @@ void BackendADMM<T>::PerformIterationFused() {
   d.m = m; d.n = n;
   d.alpha = (double)(T)opts_.alpha; d.rho = (double)rho_;
   d.out4 = scal_host_;
-  auto stage = [&](int which) { CheckHip(Api<T>::admm_stage(which, &d, st), "admm_stage"); };
 
-  auto fused = [&](int which) { CheckHip(Api<T>::admm_fused_stage(which, &d, &fused_op_, st), "admm_fused_stage"); };
-  if (fused_rounds_) fused(PROST_ADMM_FUSED_PRE);
-  else {
-    stage(PROST_ADMM_STAGE_PRE_X);
-    stage(PROST_ADMM_STAGE_PRE_Z);
-    K->Eval(z_dual_, temp3_, 1);
-    stage(PROST_ADMM_STAGE_PRE_Z2);
-  }
-
-  double cg_tol = opts_.cg_tol_min / std::pow((double)static_cast<T>(iteration_ + 1), opts_.cg_tol_pow);   // :408-410
-  cg_tol = std::max(cg_tol, opts_.cg_tol_max);
-  CglsDevice(z_dual_, x_proj_, 1, cg_tol, opts_.cg_max_iter, x_half_, z_half_, z_proj_, x_dual_);
-
-  if (fused_rounds_) fused(PROST_ADMM_FUSED_POST);
-  else {
-    stage(PROST_ADMM_STAGE_POST_X);
-    K->Eval(z_proj_, x_proj_);
-    stage(PROST_ADMM_STAGE_POST_XZ);
-  }
+  OuterStage(PROST_ADMM_FUSED_PRE, d);
+  CglsDevice(CgTolerance());
+  OuterStage(PROST_ADMM_FUSED_POST, d);
   // an identity prox over the whole variable (prox_zero.cu:37-48: a device copy of the argument) is a buffer exchange here:
   // temp1 is rewritten from scratch by the next PRE stage (not under a captured graph, which holds the buffer addresses)
-  if (!opts_.cg_graph && prox_g_.size() == 1 && dynamic_cast<ProxZero<T>*>(prox_g_[0].get()) && prox_g_[0]->index() == 0 && prox_g_[0]->size() == n)
+  if (cg_mode_ != kCgGraph && prox_g_.size() == 1 && dynamic_cast<ProxZero<T>*>(prox_g_[0].get()) && prox_g_[0]->index() == 0 && prox_g_[0]->size() == n)
     x_half_.swap(temp1_);
   else
     for (auto& p : prox_g_) p->Eval(x_half_, temp1_, Tr, 1 / rho_);
@@ -472,14 +450,8 @@ void BackendADMM<T>::PerformIterationFused() {
 
   if (iteration_ == 0 || (iteration_ % (size_t)opts_.residual_iter) == 0) {                            // :535-616
     d.x_half = x_half_.data(); d.temp1 = temp1_.data();
-    if (fused_rounds_) fused(PROST_ADMM_FUSED_RES);
-    else {
-      K->Eval(tmp_m_, x_half_);
-      stage(PROST_ADMM_STAGE_RES_Z);
-      K->EvalAdjoint(tmp_n_, tmp_m_);
-      stage(PROST_ADMM_STAGE_RES_X);                     // the fold writes the four norms to pinned host memory
-    }
-    CheckHip(prost_hip_stream_synchronize(st), "sync");
+    OuterStage(PROST_ADMM_FUSED_RES, d);
+    CheckHip(prost_hip_stream_synchronize(CurrentStream()), "sync");
     FinishResiduals((double)(T)scal_host_[0], (double)(T)scal_host_[1], (double)(T)scal_host_[2], (double)(T)scal_host_[3]);
   }
 }
@@ -499,9 +471,7 @@ void BackendADMM<T>::PerformIterationUnfused() {
   CheckHip(prost_hip_memcpy_d2d(x_proj_.data(), temp3_.data(), n * sizeof(T), st), "copy");          // CG warm start
   Gemv('n', (T)-1, temp1_, (T)1, z_dual_);
 
-  double cg_tol = opts_.cg_tol_min / std::pow((double)static_cast<T>(iteration_ + 1), opts_.cg_tol_pow);   // :408-410
-  cg_tol = std::max(cg_tol, opts_.cg_tol_max);
-  Cgls(z_dual_, x_proj_, 1, cg_tol, opts_.cg_max_iter, x_half_, z_half_, z_proj_, x_dual_, last_cg_iters_);
+  Cgls(z_dual_, x_proj_, 1, CgTolerance(), opts_.cg_max_iter, x_half_, z_half_, z_proj_, x_dual_, last_cg_iters_);
   cg_iters_valid_ = true;
 
   CheckHip(prost_hip_memcpy_d2d(temp3_.data(), x_proj_.data(), n * sizeof(T), st), "copy");

@@ -807,35 +807,15 @@ static unsigned OpLaunchSlots() {
 /// dualized operator keep the separate products.
 template <typename T>
 bool BackendPDHG<T>::DescribeGenericOperator(bool stencils_only) {
-  auto linop = this->problem_->linop();
-  if (dynamic_cast<DualLinearOperator<T>*>(linop.get())) return false;
-  const auto& blocks = linop->blocks();
-  if (blocks.empty() || blocks.size() > (size_t)PROST_HIP_OP_MAX_BLOCKS) return false;
   prost_hip_fused_op op;
-  std::memset(&op, 0, sizeof(op));
-  for (const auto& b : blocks) {
-    BlockDesc bd;
-    if (!b->describe(bd)) return false;
-    prost_hip_op_block& o = op.block[op.nblocks++];
-    o.row = b->row(); o.col = b->col(); o.nrows = b->nrows(); o.ncols = b->ncols();
-    if (bd.kind == BlockDesc::kSparse) {
-      o.kind = PROST_OP_CSR;
-      // (a stencil written out row by row: K and K^T run from row patterns)
-      if (stencils_only && !(bd.ids && bd.ids_t)) return false;
-      // (CSR rows without patterns are walked lane by lane inside the prox launches: beyond ~6 entries per row that is an order of magnitude
-      // slower than the stand-alone product with its cooperating lanes -- example_deblurring.m's 15-tap motion blur: 367 against 4 855
-      // iterations/s at 512 x 512 x 3 -- so such operators keep the separate products under every option)
-      if (!(bd.ids && bd.ids_t) && bd.nnz > 6 * std::min(b->nrows(), b->ncols())) return false;
-      o.val = bd.val; o.ptr = bd.ptr; o.ind = bd.ind; o.val_t = bd.val_t; o.ptr_t = bd.ptr_t; o.ind_t = bd.ind_t;
-      o.ids = bd.ids; o.pptr = bd.pptr; o.rel = bd.rel; o.pval = bd.pval; o.ids_t = bd.ids_t; o.pptr_t = bd.pptr_t; o.rel_t = bd.rel_t; o.pval_t = bd.pval_t;
-      o.anchor = bd.anchor; o.anchor_t = bd.anchor_t;
-    } else if ((bd.kind == BlockDesc::kGradient2D || bd.kind == BlockDesc::kGradient3D) && !bd.label_first) {
-      o.kind = bd.kind == BlockDesc::kGradient2D ? PROST_OP_GRAD2D : PROST_OP_GRAD3D;
-      o.nx = bd.nx; o.ny = bd.ny; o.L = bd.L;
-    } else {
-      return false;
-    }
-  }
+  const bool described = DescribeOperatorTable<T>(*this->problem_->linop(), op, [&](const Block<T>& b, const BlockDesc& bd) {
+    const bool patterns = bd.ids && bd.ids_t;          // (a stencil written out row by row: K and K^T run from row patterns)
+    // (CSR rows without patterns are walked lane by lane inside the prox launches: beyond ~6 entries per row that is an order of magnitude
+    // slower than the stand-alone product with its cooperating lanes -- example_deblurring.m's 15-tap motion blur: 367 against 4 855
+    // iterations/s at 512 x 512 x 3 -- so such operators keep the separate products under every option)
+    return patterns || (!stencils_only && bd.nnz <= 6 * std::min(b.nrows(), b.ncols()));
+  });
+  if (!described) return false;
   if (prost_hip_prox_elem_arg_op_supported(&op, this->problem_->nrows(), this->problem_->ncols(), dtype_id<T>()) != 1) return false;
   gen_op_ = op;
   return true;

@@ -674,4 +674,32 @@ void DualLinearOperator<T>::EvalAdjoint(device_vector<T>& result, const device_v
 template class DualLinearOperator<float>;
 template class DualLinearOperator<double>;
 
+// ---- the operator as a block table ----
+template <typename T>
+bool DescribeOperatorTable(const LinearOperator<T>& linop, prost_hip_fused_op& op, const std::function<bool(const Block<T>&, const BlockDesc&)>& accept_sparse) {
+  std::memset(&op, 0, sizeof(op));
+  if (dynamic_cast<const DualLinearOperator<T>*>(&linop)) return false;
+  const auto& blocks = linop.blocks();
+  if (blocks.empty() || blocks.size() > (size_t)PROST_HIP_OP_MAX_BLOCKS) return false;
+  for (const auto& b : blocks) {
+    BlockDesc bd;
+    if (!b->describe(bd)) return false;
+    prost_hip_op_block& o = op.block[op.nblocks++];
+    o.row = b->row(); o.col = b->col(); o.nrows = b->nrows(); o.ncols = b->ncols();
+    if (bd.kind == BlockDesc::kSparse) {
+      if (!accept_sparse(*b, bd)) return false;
+      o.kind = PROST_OP_CSR;
+      o.val = bd.val; o.ptr = bd.ptr; o.ind = bd.ind; o.val_t = bd.val_t; o.ptr_t = bd.ptr_t; o.ind_t = bd.ind_t;
+      o.ids = bd.ids; o.pptr = bd.pptr; o.rel = bd.rel; o.pval = bd.pval; o.ids_t = bd.ids_t; o.pptr_t = bd.pptr_t; o.rel_t = bd.rel_t; o.pval_t = bd.pval_t;
+      o.anchor = bd.anchor; o.anchor_t = bd.anchor_t;
+    } else if ((bd.kind == BlockDesc::kGradient2D || bd.kind == BlockDesc::kGradient3D) && !bd.label_first) {
+      o.kind = bd.kind == BlockDesc::kGradient2D ? PROST_OP_GRAD2D : PROST_OP_GRAD3D;
+      o.nx = bd.nx; o.ny = bd.ny; o.L = bd.L;
+    } else return false;
+  }
+  return true;
+}
+template bool DescribeOperatorTable<float>(const LinearOperator<float>&, prost_hip_fused_op&, const std::function<bool(const Block<float>&, const BlockDesc&)>&);
+template bool DescribeOperatorTable<double>(const LinearOperator<double>&, prost_hip_fused_op&, const std::function<bool(const Block<double>&, const BlockDesc&)>&);
+
 }  // namespace prost

@@ -484,6 +484,39 @@ def test_admm_matches_oracle(precision, dtype, device_cg, fused_rounds):
 
 
 @pytest.mark.parametrize("precision,dtype", PRECISIONS)
+@pytest.mark.parametrize("pixel_rounds", [True, False])
+def test_admm_timed_rounds_leave_the_same_state(precision, dtype, pixel_rounds):
+    """The CG rounds that stamp events kernel by kernel (prost_hip_cgls_round_timed / _pixel_round_timed, one round of every solve
+    with sample_every = 1) compute what the plain rounds compute, bit for bit, and kernel timing reports exactly the kernels of a
+    round -- two for the pixel rounds, four with the operator inside the stages.  24 x 20: all three operator blocks, the vector
+    and the scalar tails."""
+    prost.set_precision(precision)
+    prob = tvl1_like_problem(24, 20)
+    b = prost.backend.admm(rho0=1, residual_iter=2)
+    b[1]["pixel_rounds"] = pixel_rounds
+    o = prost.options(max_iters=100, num_cback_calls=0, verbose=False)
+    states, kernels = [], None
+    for timed in (True, False):
+        s = prost.Solver(prob, b, o)
+        info = s.iterate(6, time_kernels=timed, sample_every=1)
+        states.append(s.state())
+        s.destroy()
+        if timed:
+            kernels = info["kernels"]
+        else:
+            assert info["kernels"] == {}
+    for st in states:
+        assert st["path"] == ("admm:pixel-op" if pixel_rounds else "admm:fused-op")
+    assert_same_iterates(states[0], states[1])
+    for name in ("rho", "cg_iterations", "primal_res", "dual_res"):
+        assert states[0][name] == states[1][name], name
+    names = ["cg_pixel_pq_kernel", "cg_pixel_xrs_kernel"] if pixel_rounds else ["op_stage_kernel<EpiFwdQ>", "cg_step_xr2_kernel", "op_stage_kernel<EpiAdjS>", "cg_step_p2_kernel"]
+    assert sorted(kernels) == sorted(names)
+    for name in names:
+        assert kernels[name]["sampled"] >= 1 and kernels[name]["avg_ms"] > 0, (name, kernels[name])
+
+
+@pytest.mark.parametrize("precision,dtype", PRECISIONS)
 def test_operator_norm_estimate_equals_the_oracle_bit_for_bit(precision, dtype):
     """Problem::normest (problem.cu:429-500) divides the initial step sizes when the estimate is further than 0.1 from 1
     (backend_pdhg.cu:274-286).  Its two norms per round are reductions the reference leaves to thrust; here and in the oracle they are
