@@ -1,6 +1,7 @@
 // prost/prox/elemop/spectral_common.hpp -- what the spectral operations (elem_operation_singular_nx2.hpp,
-// elem_operation_eigen_2x2.hpp, elem_operation_eigen_3x3.hpp) share: the scalar prox convention on a singular value or an
-// eigenvalue, and the symmetric 2x2 / 3x3 eigendecompositions.
+// elem_operation_eigen_2x2.hpp, elem_operation_eigen_3x3.hpp, elem_operation_eigen_nxn.hpp, elem_operation_mass_norm.hpp) share: the
+// scalar prox convention on a singular value or an eigenvalue, the symmetric 2x2 / 3x3 / N x N eigendecompositions, and the parts
+// of the n x n Jacobi that do not depend on how many lanes share a matrix.
 //
 // Everything here is fp64 whatever the data type is: the reference decomposes in double for float and double data alike
 // (elem_operation_eigen_3x3.hpp:306-325 there), and so do these.  The decompositions are Jacobi rotations, not the
@@ -107,6 +108,96 @@ __host__ __device__ __forceinline__ void SymEig3x3(double a00, double a01, doubl
   v[0][0] = v00; v[0][1] = v01; v[0][2] = v02;
   v[1][0] = v10; v[1][1] = v11; v[1][2] = v12;
   v[2][0] = v20; v[2][1] = v21; v[2][2] = v22;
+}
+
+// ---- n x n (elem_operation_eigen_nxn.hpp, elem_operation_mass_norm.hpp, prost_amd/csrc/kernels_prox_eigen_nxn.hip) ----------------
+// What does not depend on how many lanes share a matrix is written once here: the rotation angle (JacobiAngle above), the order
+// in which the planes are visited (RoundRobinPair), the convergence test of a sweep (JacobiConverged), the two-sided update of
+// a 2x2 block (JacobiBlock) and the scalar prox (SpectralProx1D above).
+
+/// largest n of eigen_nxn (sum_eigen_nxn.m:5)
+constexpr int kEigenNxNMax = 32;
+/// Sweep cap of the n x n decompositions.  Parallel-ordered Jacobi needed at most 8 sweeps to pass JacobiConverged on the parity
+/// inputs and the special matrices up to n = 32 (docs/rounds/r11.md); the cap is twice that.  Every sweep loop is a `for` up to
+/// this constant, so NaN or Inf input ends after kJacobiSweepsNxN sweeps.
+constexpr int kJacobiSweepsNxN = 16;
+
+/// a sweep is skipped, and the decomposition ends, when the off-diagonal part no longer changes the diagonal sum (both sums of
+/// absolute values over the matrix).  True for the zero matrix; false whenever a NaN is involved.
+__host__ __device__ __forceinline__ bool JacobiConverged(double diag, double off) { return diag + off == diag; }
+
+/// Round-robin (circle method) schedule for even m: in round 0..m-2, slot 0..m/2-1 names the pair p < q; the m/2 pairs of a round
+/// are disjoint, and the m-1 rounds hold every unordered pair of 0..m-1 exactly once.  An odd n plays with m = n + 1: the pair
+/// that holds index n is a bye.  No division: the indices are reduced by conditional subtraction.
+__host__ __device__ __forceinline__ void RoundRobinPair(int m, int round, int slot, int& p, int& q) {
+  const int r = m - 1;
+  int a = r, b = round;
+  if (slot != 0) {
+    a = round + slot;
+    if (a >= r) a -= r;
+    b = round - slot;
+    if (b < 0) b += r;
+  }
+  p = a < b ? a : b;
+  q = a < b ? b : a;
+}
+
+/// B <- J_k^T B J_l for the 2x2 block B = [x00 x01; x10 x11] whose rows are the pair k and whose columns are the pair l of a round,
+/// J = [c s; -s c] as JacobiAngle returns it
+__host__ __device__ __forceinline__ void JacobiBlock(double ck, double sk, double cl, double sl, double& x00, double& x01, double& x10, double& x11) {
+  const double y00 = ck * x00 - sk * x10, y01 = ck * x01 - sk * x11;
+  const double y10 = sk * x00 + ck * x10, y11 = sk * x01 + ck * x11;
+  x00 = cl * y00 - sl * y01; x01 = sl * y00 + cl * y01;
+  x10 = cl * y10 - sl * y11; x11 = sl * y10 + cl * y11;
+}
+
+/// Symmetric N x N eigendecomposition, N a compile-time constant: cyclic Jacobi like SymEig3x3, every index a constant after
+/// unrolling, so the matrix lives in registers.  In: the upper triangle of a (i <= j).  Out: a[j][j] the eigenvalues and the columns
+/// v[.][j] with A = V diag V^T (not ordered); the strict upper triangle is left at rounding level, the lower one is never touched.
+/// Returns the number of sweeps that ran.
+template <int N>
+__host__ __device__ __forceinline__ int SymEigN(double (&a)[N][N], double (&v)[N][N]) {
+#pragma unroll
+  for (int i = 0; i < N; i++)
+#pragma unroll
+    for (int j = 0; j < N; j++) v[i][j] = i == j ? 1. : 0.;
+  int sweep = 0;
+#pragma unroll 1
+  for (; sweep < kJacobiSweepsNxN; sweep++) {
+    double off = 0., diag = 0.;
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+      diag += t_abs(a[i][i]);
+#pragma unroll
+      for (int j = i + 1; j < N; j++) off += t_abs(a[i][j]);
+    }
+    if (JacobiConverged(diag, off)) break;
+#pragma unroll
+    for (int p = 0; p < N - 1; p++) {
+#pragma unroll
+      for (int q = p + 1; q < N; q++) {
+        double c, s, t;
+        JacobiAngle(a[p][p], a[q][q], a[p][q], c, s, t);
+        a[p][p] -= t * a[p][q];
+        a[q][q] += t * a[p][q];
+        a[p][q] = 0.;
+#pragma unroll
+        for (int r = 0; r < N; r++) {
+          if (r != p && r != q) {
+            double& x = r < p ? a[r][p] : a[p][r];
+            double& y = r < q ? a[r][q] : a[q][r];
+            const double xx = x, yy = y;
+            x = c * xx - s * yy;
+            y = s * xx + c * yy;
+          }
+          const double vp = v[r][p], vq = v[r][q];
+          v[r][p] = c * vp - s * vq;
+          v[r][q] = s * vp + c * vq;
+        }
+      }
+    }
+  }
+  return sweep;
 }
 
 }  // namespace elemop

@@ -47,7 +47,10 @@ class ProxElemDispatch : public ProxSeparableSum<T> {
 
 /// The spectral family: elem_operation:singular_nx2:* (a function of the two singular values of the n x 2 matrix a group holds,
 /// dim = 2 n), elem_operation:eigen_2x2:* and elem_operation:eigen_3x3:* (a function of the eigenvalues of the symmetrised 2x2 / 3x3
-/// matrix, dim 4 / 9).  Operation and function are run-time ids (PROST_SPECTRAL_*, PROST_FN_* / PROST_FN2D_* of prost_hip.h) of one
+/// matrix, dim 4 / 9), elem_operation:eigen_nxn:* (the same for a row-major n x n matrix, dim = n^2, n <= 32; from n = 6 on several lanes
+/// share a matrix: prost_amd/csrc/kernels_prox_eigen_nxn.hip) and elem_operation:mass4 / mass5 / ind_comass4_ball / ind_comass5_ball (mass
+/// norm of a 2-vector in R^4 / R^5, dim 6 / 10, and the projection onto the ball of its dual norm; coefficient 0 is the cost, the function
+/// id is ignored; elem_operation_eigen_nxn.hpp, elem_operation_mass_norm.hpp).  Operation and function are run-time ids (PROST_SPECTRAL_*, PROST_FN_* / PROST_FN2D_* of prost_hip.h) of one
 /// kernel family (prost_amd/csrc/kernels_prox_spectral.hip); the arithmetic is prost/prox/elemop/elem_operation_singular_nx2.hpp,
 /// _eigen_2x2.hpp, _eigen_3x3.hpp.  A dimension the operation does not take throws at construction.  The kernel reads the step size
 /// from device memory when asked to (Prox::StepView), so goldstein / boyd keep their device-resident rule on problems that use it.

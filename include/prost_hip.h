@@ -318,12 +318,27 @@ int prost_hip_prox_elem_ind_simplex_f64(double* res, const double* arg, double* 
  * from *step_dev on the device and a non-zero *stop_dev makes the kernel return without writing (both NULL or both set; `tau` is then
  * ignored).  coeff_ptr / coeff_val, the layout rule and the absence of a device sync are those of prost_hip_prox_elem; coefficient
  * vectors have one value per GROUP.  A bad (op, fn, dim) combination returns an error without launching. */
-enum { PROST_SPECTRAL_SINGULAR_NX2 = 0, PROST_SPECTRAL_EIGEN_2X2 = 1, PROST_SPECTRAL_EIGEN_3X3 = 2 };
+enum { PROST_SPECTRAL_SINGULAR_NX2 = 0, PROST_SPECTRAL_EIGEN_2X2 = 1, PROST_SPECTRAL_EIGEN_3X3 = 2,
+       /* additions (ABI version unchanged) */
+       PROST_SPECTRAL_EIGEN_NXN = 3, PROST_SPECTRAL_MASS4 = 4, PROST_SPECTRAL_IND_COMASS4_BALL = 5, PROST_SPECTRAL_MASS5 = 6,
+       PROST_SPECTRAL_IND_COMASS5_BALL = 7 };
+/* PROST_SPECTRAL_EIGEN_NXN: a function of the eigenvalues of the symmetrised row-major n x n matrix a group holds, dim = n * n, 1 <= n <= 32
+ * (include/prost/prox/elemop/elem_operation_eigen_nxn.hpp).  n <= 5: one matrix per lane in registers; n >= 6: several lanes per matrix, A
+ * and V^T in LDS (kernels_prox_eigen_nxn.hip; geometry: prost_hip_prox_eigen_nxn_plan).
+ * PROST_SPECTRAL_MASS4 / _MASS5 (dim 6 / 10): prox of the mass norm of the 2-vector in R^4 / R^5 a group holds as the upper triangle of a
+ * skew-symmetric matrix, row by row; PROST_SPECTRAL_IND_COMASS4_BALL / _COMASS5_BALL: projection onto the unit ball of the comass norm
+ * (elem_operation_mass_norm.hpp).  For these four `fn` is ignored and coeff_ptr[0] / coeff_val[0] is the cost: a weight on the norm, one
+ * value per group when a vector, multiplied onto tau in the data type (the comass ball does not depend on the step). */
 enum { PROST_FN2D_IND_L1_BALL = 100, PROST_FN2D_MOREAU_IND_L1_BALL = 101 };
 int prost_hip_prox_spectral_f32(int op, int fn, float* res, const float* arg, const float* tau_diag, double tau, const float* step_dev, const int* stop_dev,
                                 int invert_tau, size_t count, size_t dim, int interleaved, const float* const* coeff_ptr, const double* coeff_val, void* stream);
 int prost_hip_prox_spectral_f64(int op, int fn, double* res, const double* arg, const double* tau_diag, double tau, const double* step_dev, const int* stop_dev,
                                 int invert_tau, size_t count, size_t dim, int interleaved, const double* const* coeff_ptr, const double* coeff_val, void* stream);
+/* Host only, no device needed, no launch: the geometry prost_hip_prox_spectral_* uses for PROST_SPECTRAL_EIGEN_NXN at this n (1..32) and
+ * dtype (0 fp32, 1 fp64): lanes that share one matrix (a power of two <= 64; 1 on the register path), matrices per 256-lane workgroup
+ * (lanes * matrices = 256) and the LDS bytes of a workgroup (register path: the tile of the interleaved layout).  Any pointer may be
+ * NULL.  Returns non-zero for any other n or dtype. */
+int prost_hip_prox_eigen_nxn_plan(size_t n, int dtype, int* lanes_per_matrix, int* matrices_per_workgroup, size_t* lds_bytes);
 
 /* ------------------------------------------------------------------------------------------ */
 /* PDHG building blocks, generic path (src/backend/backend_pdhg.cu)                            */

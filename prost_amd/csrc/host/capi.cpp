@@ -212,6 +212,30 @@ static Prox<T>* make_spectral(int op, int fn, size_t idx, size_t size, bool diag
   return new ProxSpectral<T>(op, fn, idx, count, dim, interleaved, diagsteps, coeffs);
 }
 
+/// mass4 / mass5 / ind_comass4_ball / ind_comass5_ball: { count, dim, interleaved [, { cost }] }.  sum_mass_norm.m writes the fourth cell for
+/// n = 4 only and the reference ignores a cost for n = 5; here the cell is optional for all four names (missing: cost 1), the two
+/// mass names honour it, the two comass names ignore it.
+template <typename T>
+static Prox<T>* make_mass(int op, size_t idx, size_t size, bool diagsteps, const prost_value* data) {
+  const size_t count = (size_t)GetScalarFromCell(data, 0), dim = (size_t)GetScalarFromCell(data, 1);
+  const bool interleaved = GetScalarFromCell(data, 2) > 0.;
+  if (count * dim != size) {
+    std::stringstream ss;
+    ss << ProxSpectral<T>::OperationName(op) << ": size = " << size << " is not count * dim = " << count << " * " << dim << ".";
+    throw Exception(ss.str());
+  }
+  std::array<std::vector<T>, 7> coeffs;
+  for (auto& c : coeffs) c.assign(1, (T)0);
+  coeffs[0][0] = (T)1;
+  const bool is_mass = op == PROST_SPECTRAL_MASS4 || op == PROST_SPECTRAL_MASS5;
+  if (is_mass && data && data->kind == PROST_VALUE_CELL && data->cells.size() > 3 && data->cells[3]) {
+    std::vector<double> cost = GetVector(cell_at(data->cells[3], 0));
+    if (cost.size() != 1 && cost.size() != count) throw Exception(std::string(ProxSpectral<T>::OperationName(op)) + ": size of the cost should be either 1 or count.");
+    coeffs[0] = std::vector<T>(cost.begin(), cost.end());
+  }
+  return new ProxSpectral<T>(op, 0, idx, count, dim, interleaved, diagsteps, coeffs);
+}
+
 template <typename T>
 std::map<std::string, typename Factory<T>::ProxFactory>& Factory<T>::prox_reg() {
   static std::map<std::string, ProxFactory> reg;
@@ -225,6 +249,7 @@ std::map<std::string, typename Factory<T>::ProxFactory>& Factory<T>::prox_reg() 
     for (int fn = 0; fn < PROST_FN_COUNT; fn++) {
       reg[std::string("elem_operation:eigen_2x2:") + kFunctionNames[fn]] = [fn](size_t idx, size_t size, bool ds, const prost_value* d) { return make_spectral<T>(PROST_SPECTRAL_EIGEN_2X2, fn, idx, size, ds, d); };
       reg[std::string("elem_operation:eigen_3x3:") + kFunctionNames[fn]] = [fn](size_t idx, size_t size, bool ds, const prost_value* d) { return make_spectral<T>(PROST_SPECTRAL_EIGEN_3X3, fn, idx, size, ds, d); };
+      reg[std::string("elem_operation:eigen_nxn:") + kFunctionNames[fn]] = [fn](size_t idx, size_t size, bool ds, const prost_value* d) { return make_spectral<T>(PROST_SPECTRAL_EIGEN_NXN, fn, idx, size, ds, d); };
     }
     // singular_nx2: the ten functions of the reference's table (zero .. huber) under "sum_1d:<fn>".  The builder concatenates its `fun`
     // argument as it stands (sum_singular_nx2.m:28), so sum_singular_nx2(dim, il, 'ind_leq0', ...) asks for the name WITHOUT "sum_1d:";
@@ -236,6 +261,10 @@ std::map<std::string, typename Factory<T>::ProxFactory>& Factory<T>::prox_reg() 
     }
     reg["elem_operation:singular_nx2:ind_l1_ball"] = [](size_t idx, size_t size, bool ds, const prost_value* d) { return make_spectral<T>(PROST_SPECTRAL_SINGULAR_NX2, PROST_FN2D_IND_L1_BALL, idx, size, ds, d); };
     reg["elem_operation:singular_nx2:moreau:ind_l1_ball"] = [](size_t idx, size_t size, bool ds, const prost_value* d) { return make_spectral<T>(PROST_SPECTRAL_SINGULAR_NX2, PROST_FN2D_MOREAU_IND_L1_BALL, idx, size, ds, d); };
+    reg["elem_operation:mass4"] = [](size_t idx, size_t size, bool ds, const prost_value* d) { return make_mass<T>(PROST_SPECTRAL_MASS4, idx, size, ds, d); };
+    reg["elem_operation:mass5"] = [](size_t idx, size_t size, bool ds, const prost_value* d) { return make_mass<T>(PROST_SPECTRAL_MASS5, idx, size, ds, d); };
+    reg["elem_operation:ind_comass4_ball"] = [](size_t idx, size_t size, bool ds, const prost_value* d) { return make_mass<T>(PROST_SPECTRAL_IND_COMASS4_BALL, idx, size, ds, d); };
+    reg["elem_operation:ind_comass5_ball"] = [](size_t idx, size_t size, bool ds, const prost_value* d) { return make_mass<T>(PROST_SPECTRAL_IND_COMASS5_BALL, idx, size, ds, d); };
     reg["moreau"] = [](size_t, size_t, bool, const prost_value* d) -> Prox<T>* { return new ProxMoreau<T>(Factory<T>::CreateProx(cell_at(d, 0))); };
     reg["zero"] = [](size_t idx, size_t size, bool, const prost_value*) -> Prox<T>* { return new ProxZero<T>(idx, size); };
     reg["elem_operation:ind_sum"] = [](size_t idx, size_t, bool ds, const prost_value* d) -> Prox<T>* {

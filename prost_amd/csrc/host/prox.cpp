@@ -136,10 +136,20 @@ bool ProxElemDispatch<T>::supports_op_source() const {
 template class ProxElemDispatch<float>;
 template class ProxElemDispatch<double>;
 
-// ---- spectral: singular_nx2 / eigen_2x2 / eigen_3x3 ----
+// ---- spectral: singular_nx2 / eigen_2x2 / eigen_3x3 / eigen_nxn / mass4 / mass5 / ind_comass4_ball / ind_comass5_ball ----
 template <typename T>
 const char* ProxSpectral<T>::OperationName(int op) {
-  return op == PROST_SPECTRAL_SINGULAR_NX2 ? "singular_nx2" : op == PROST_SPECTRAL_EIGEN_2X2 ? "eigen_2x2" : op == PROST_SPECTRAL_EIGEN_3X3 ? "eigen_3x3" : "spectral";
+  switch (op) {
+    case PROST_SPECTRAL_SINGULAR_NX2: return "singular_nx2";
+    case PROST_SPECTRAL_EIGEN_2X2: return "eigen_2x2";
+    case PROST_SPECTRAL_EIGEN_3X3: return "eigen_3x3";
+    case PROST_SPECTRAL_EIGEN_NXN: return "eigen_nxn";
+    case PROST_SPECTRAL_MASS4: return "mass4";
+    case PROST_SPECTRAL_IND_COMASS4_BALL: return "ind_comass4_ball";
+    case PROST_SPECTRAL_MASS5: return "mass5";
+    case PROST_SPECTRAL_IND_COMASS5_BALL: return "ind_comass5_ball";
+  }
+  return "spectral";
 }
 template <typename T>
 ProxSpectral<T>::ProxSpectral(int op, int fn, size_t index, size_t count, size_t dim, bool interleaved, bool diagsteps,
@@ -149,7 +159,16 @@ ProxSpectral<T>::ProxSpectral(int op, int fn, size_t index, size_t count, size_t
   if (op == PROST_SPECTRAL_SINGULAR_NX2 && (dim == 0 || dim % 2 != 0)) ss << "singular_nx2: dim = " << dim << ", but a group is an n x 2 matrix: dim has to be even.";
   else if (op == PROST_SPECTRAL_EIGEN_2X2 && dim != 4) ss << "eigen_2x2: dim = " << dim << ", but a group is a 2 x 2 matrix: dim has to be 4.";
   else if (op == PROST_SPECTRAL_EIGEN_3X3 && dim != 9) ss << "eigen_3x3: dim = " << dim << ", but a group is a 3 x 3 matrix: dim has to be 9.";
-  else if (op != PROST_SPECTRAL_SINGULAR_NX2 && op != PROST_SPECTRAL_EIGEN_2X2 && op != PROST_SPECTRAL_EIGEN_3X3) ss << "spectral prox: unknown operation id " << op << ".";
+  else if (op == PROST_SPECTRAL_EIGEN_NXN) {
+    size_t n = 0;                                      // dim comes from the description: at most 32 steps whatever it is
+    for (size_t k = 1; k <= 32 && n == 0; k++)
+      if (k * k == dim) n = k;
+    if (n == 0) ss << "eigen_nxn: dim = " << dim << ", but a group is an n x n matrix with 1 <= n <= 32: dim has to be one of 1, 4, 9, .., 1024.";
+  } else if ((op == PROST_SPECTRAL_MASS4 || op == PROST_SPECTRAL_IND_COMASS4_BALL) && dim != 6)
+    ss << OperationName(op) << ": Wrong dimension in mass norm prox: dim = " << dim << ", but a 2-vector in R^4 has 6 components.";
+  else if ((op == PROST_SPECTRAL_MASS5 || op == PROST_SPECTRAL_IND_COMASS5_BALL) && dim != 10)
+    ss << OperationName(op) << ": Wrong dimension in mass norm prox: dim = " << dim << ", but a 2-vector in R^5 has 10 components.";
+  else if (op < PROST_SPECTRAL_SINGULAR_NX2 || op > PROST_SPECTRAL_IND_COMASS5_BALL) ss << "spectral prox: unknown operation id " << op << ".";
   if (!ss.str().empty()) throw Exception(ss.str());
   for (int i = 0; i < 7; i++)
     if (coeffs_[i].empty()) throw Exception(std::string(OperationName(op)) + ": empty coefficient vector passed.");

@@ -18,19 +18,15 @@
 //     next to a stop word (Prox::StepView): a raised stop word ends the kernel before it touches the result.
 // singular_nx2 with dim > 12 streams the group twice over HBM (once for M^T M, once for the product), one group per lane.
 // No device synchronisation; launch-configuration errors surface through hipGetLastError.
-#include "common.hpp"
-#include "device_math.hpp"
+#include "prox_spectral.hpp"
 #include "prost/prox/elemop/elem_operation_eigen_2x2.hpp"
 #include "prost/prox/elemop/elem_operation_eigen_3x3.hpp"
+#include "prost/prox/elemop/elem_operation_eigen_nxn.hpp"
+#include "prost/prox/elemop/elem_operation_mass_norm.hpp"
 #include "prost/prox/elemop/elem_operation_singular_nx2.hpp"
 
 namespace prost_hip {
 
-/// the scalar function as a run-time id: one scalar branch per wavefront (fn is a kernel argument)
-struct RtFun1D {
-  int fn;
-  __device__ __forceinline__ double operator()(double x0, double tau, double alpha, double beta) const { return f1d_apply<double>(fn, x0, tau, alpha, beta); }
-};
 struct RtFun2D {
   int fn;
   __device__ __forceinline__ void operator()(double y1, double y2, double& x1, double& x2, double tau, double alpha, double beta) const {
@@ -43,32 +39,27 @@ struct RtFun2D {
   }
 };
 
-template <class T>
-struct SpectralArgs {
-  T* res; const T* arg; const T* tau_diag;
-  T tau; const T* step; const int* stop;       // step != null: the scalar step is *step, and *stop != 0 ends the kernel
-  bool invert_tau;
-  size_t count;
-  int fn;
-  const T* cp[7]; T cv[7];                     // per-group coefficient vectors (or null) and the scalar values
-};
-
-template <class T, int N> struct alignas(sizeof(T) * N) SpPack { T v[N]; };
-
-template <class T>
-__device__ __forceinline__ bool spectral_step(const SpectralArgs<T>& p, T& tau) {
-  tau = p.tau;
-  if (p.step == nullptr) return true;
-  if (*p.stop != 0) return false;
-  tau = *p.step;
-  return true;
-}
-
 template <class T, int OP, int DIM>
 __device__ __forceinline__ void spectral_apply(T (&r)[DIM], const T (&a)[DIM], double tau, const T* c, int fn) {
   if constexpr (OP == PROST_SPECTRAL_SINGULAR_NX2) prost::elemop::SingularNx2Apply<T, double>(r, a, (size_t)(DIM / 2), tau, c, RtFun2D{fn});
   else if constexpr (OP == PROST_SPECTRAL_EIGEN_2X2) prost::elemop::Eigen2x2Apply<T>(r, a, tau, c, RtFun1D{fn});
-  else prost::elemop::Eigen3x3Apply<T>(r, a, tau, c, RtFun1D{fn});
+  else if constexpr (OP == PROST_SPECTRAL_EIGEN_3X3) prost::elemop::Eigen3x3Apply<T>(r, a, tau, c, RtFun1D{fn});
+  else if constexpr (OP == PROST_SPECTRAL_EIGEN_NXN) {
+    // a symmetrised matrix and a symmetric result read the same row by row and column by column: n = 2, 3 are the existing operations
+    if constexpr (DIM == 4) prost::elemop::Eigen2x2Apply<T>(r, a, tau, c, RtFun1D{fn});
+    else if constexpr (DIM == 9) prost::elemop::Eigen3x3Apply<T>(r, a, tau, c, RtFun1D{fn});
+    else prost::elemop::EigenNApply<T, DIM == 1 ? 1 : DIM == 16 ? 4 : 5>(r, a, tau, c, RtFun1D{fn});
+  } else if constexpr (OP == PROST_SPECTRAL_MASS4) prost::elemop::MassNormApply<T, 4, false>(r, a, tau);
+  else if constexpr (OP == PROST_SPECTRAL_IND_COMASS4_BALL) prost::elemop::MassNormApply<T, 4, true>(r, a, tau);
+  else if constexpr (OP == PROST_SPECTRAL_MASS5) prost::elemop::MassNormApply<T, 5, false>(r, a, tau);
+  else prost::elemop::MassNormApply<T, 5, true>(r, a, tau);
+}
+
+/// the scalar step of a group: for the mass operations the cost (coefficient 0) is a weight on it, multiplied in T
+template <class T, int OP>
+__device__ __forceinline__ T spectral_group_tau(T tau_scal, const T* c) {
+  if constexpr (OP >= PROST_SPECTRAL_MASS4) return tau_scal * c[0];
+  else return tau_scal;
 }
 
 // 256 * DIM contiguous values between HBM and the LDS tile of a workgroup; `valid` of them exist (the last workgroup).
@@ -77,8 +68,9 @@ template <class T, int DIM, bool LOAD>
 __device__ __forceinline__ void spectral_tile_copy(T* tile, T* hbm, size_t valid) {
   constexpr int V = 16 / (int)sizeof(T);
   const bool wide = (reinterpret_cast<uintptr_t>(hbm) & 15u) == 0;
-#pragma unroll
-  for (int it = 0; it < (DIM + V - 1) / V; it++) {
+  constexpr int kTrips = (DIM + V - 1) / V, kUnroll = DIM > 12 ? 1 : kTrips;      // the 4x4 / 5x5 tiles: a rolled loop, fewer scalar registers
+#pragma unroll kUnroll
+  for (int it = 0; it < kTrips; it++) {
     const int i = (it * kBlock + (int)threadIdx.x) * V;
     if (i >= kBlock * DIM) continue;
     if (wide && (size_t)(i + V) <= valid) {
@@ -110,7 +102,7 @@ __global__ void __launch_bounds__(kBlock) spectral_kernel(SpectralArgs<T> p) {
       T c[7];
 #pragma unroll
       for (int k = 0; k < 7; k++) c[k] = p.cp[k] != nullptr ? p.cp[k][g] : p.cv[k];
-      spectral_apply<T, OP, DIM>(r, a, prost::elemop::SpectralStep(tau_scal, p.tau_diag[g * DIM], p.invert_tau), c, p.fn);
+      spectral_apply<T, OP, DIM>(r, a, prost::elemop::SpectralStep(spectral_group_tau<T, OP>(tau_scal, c), p.tau_diag[g * DIM], p.invert_tau), c, p.fn);
 #pragma unroll
       for (int k = 0; k < DIM; k++) tile[threadIdx.x * DIM + k] = r[k];      // a lane overwrites the slots it has read itself
     }
@@ -118,14 +110,27 @@ __global__ void __launch_bounds__(kBlock) spectral_kernel(SpectralArgs<T> p) {
     spectral_tile_copy<T, DIM, false>(tile, p.res + g0 * DIM, valid);
   } else {
     if (!live) return;
+    if constexpr (DIM > 12) {
+      // 25 component offsets k * count kept as wave-uniform 64-bit values would not fit the scalar registers: the address walks in the lane
+      const T* ap = p.arg + g;
 #pragma unroll
-    for (int k = 0; k < DIM; k++) a[k] = p.arg[g + p.count * k];
+      for (int k = 0; k < DIM; k++) { a[k] = *ap; ap += p.count; asm volatile("" : "+v"(ap)); }
+    } else {
+#pragma unroll
+      for (int k = 0; k < DIM; k++) a[k] = p.arg[g + p.count * k];
+    }
     T c[7];
 #pragma unroll
     for (int k = 0; k < 7; k++) c[k] = p.cp[k] != nullptr ? p.cp[k][g] : p.cv[k];
-    spectral_apply<T, OP, DIM>(r, a, prost::elemop::SpectralStep(tau_scal, p.tau_diag[g], p.invert_tau), c, p.fn);
+    spectral_apply<T, OP, DIM>(r, a, prost::elemop::SpectralStep(spectral_group_tau<T, OP>(tau_scal, c), p.tau_diag[g], p.invert_tau), c, p.fn);
+    if constexpr (DIM > 12) {
+      T* rp = p.res + g;
 #pragma unroll
-    for (int k = 0; k < DIM; k++) p.res[g + p.count * k] = r[k];
+      for (int k = 0; k < DIM; k++) { *rp = r[k]; rp += p.count; asm volatile("" : "+v"(rp)); }
+    } else {
+#pragma unroll
+      for (int k = 0; k < DIM; k++) p.res[g + p.count * k] = r[k];
+    }
   }
 }
 
@@ -155,12 +160,21 @@ static int launch_spectral(int op, int fn, T* res, const T* arg, const T* tau_di
                            size_t count, size_t dim, int interleaved, const T* const* coeff_ptr, const double* coeff_val, void* stream) {
   const bool fn1d = fn >= 0 && fn < PROST_FN_COUNT;
   const bool fn2d = fn == PROST_FN2D_IND_L1_BALL || fn == PROST_FN2D_MOREAU_IND_L1_BALL;
+  int n_side = 0;
   if (op == PROST_SPECTRAL_SINGULAR_NX2) {
     if (!(fn1d || fn2d)) { set_error("prox_spectral: unknown function id"); return 1; }
     if (dim == 0 || dim % 2 != 0) { set_error("prox_spectral: singular_nx2 needs an even dim"); return 1; }
   } else if (op == PROST_SPECTRAL_EIGEN_2X2 || op == PROST_SPECTRAL_EIGEN_3X3) {
     if (!fn1d) { set_error("prox_spectral: unknown function id"); return 1; }
     if (dim != (op == PROST_SPECTRAL_EIGEN_2X2 ? 4u : 9u)) { set_error("prox_spectral: eigen_2x2 needs dim 4, eigen_3x3 dim 9"); return 1; }
+  } else if (op == PROST_SPECTRAL_EIGEN_NXN) {
+    if (!fn1d) { set_error("prox_spectral: unknown function id"); return 1; }
+    n_side = prost::elemop::EigenNxNSide(dim);
+    if (n_side < 1 || n_side > prost::elemop::kEigenNxNMax) { set_error("prox_spectral: eigen_nxn needs dim = n * n with 1 <= n <= 32"); return 1; }
+  } else if (op == PROST_SPECTRAL_MASS4 || op == PROST_SPECTRAL_IND_COMASS4_BALL) {
+    if (dim != 6) { set_error("prox_spectral: mass4 and ind_comass4_ball need dim 6"); return 1; }
+  } else if (op == PROST_SPECTRAL_MASS5 || op == PROST_SPECTRAL_IND_COMASS5_BALL) {
+    if (dim != 10) { set_error("prox_spectral: mass5 and ind_comass5_ball need dim 10"); return 1; }
   } else { set_error("prox_spectral: unknown operation id"); return 1; }
   if ((step_dev == nullptr) != (stop_dev == nullptr)) { set_error("prox_spectral: the device step and the stop word come together"); return 1; }
   if (count == 0) return 0;
@@ -177,6 +191,20 @@ static int launch_spectral(int op, int fn, T* res, const T* arg, const T* tau_di
   const bool il = interleaved != 0;
   if (op == PROST_SPECTRAL_EIGEN_2X2) launch_instance<T, PROST_SPECTRAL_EIGEN_2X2, 4>(p, il, grid, s);
   else if (op == PROST_SPECTRAL_EIGEN_3X3) launch_instance<T, PROST_SPECTRAL_EIGEN_3X3, 9>(p, il, grid, s);
+  else if (op == PROST_SPECTRAL_EIGEN_NXN) {
+    if (n_side >= kEigenCoopMinN) return launch_eigen_nxn_coop<T>(p, n_side, il, s);         // several lanes per matrix, A and V^T in LDS
+    switch (n_side) {
+      case 1: launch_instance<T, PROST_SPECTRAL_EIGEN_NXN, 1>(p, il, grid, s); break;
+      case 2: launch_instance<T, PROST_SPECTRAL_EIGEN_NXN, 4>(p, il, grid, s); break;
+      case 3: launch_instance<T, PROST_SPECTRAL_EIGEN_NXN, 9>(p, il, grid, s); break;
+      case 4: launch_instance<T, PROST_SPECTRAL_EIGEN_NXN, 16>(p, il, grid, s); break;
+      default: launch_instance<T, PROST_SPECTRAL_EIGEN_NXN, 25>(p, il, grid, s); break;
+    }
+  }
+  else if (op == PROST_SPECTRAL_MASS4) launch_instance<T, PROST_SPECTRAL_MASS4, 6>(p, il, grid, s);
+  else if (op == PROST_SPECTRAL_IND_COMASS4_BALL) launch_instance<T, PROST_SPECTRAL_IND_COMASS4_BALL, 6>(p, il, grid, s);
+  else if (op == PROST_SPECTRAL_MASS5) launch_instance<T, PROST_SPECTRAL_MASS5, 10>(p, il, grid, s);
+  else if (op == PROST_SPECTRAL_IND_COMASS5_BALL) launch_instance<T, PROST_SPECTRAL_IND_COMASS5_BALL, 10>(p, il, grid, s);
   else switch (dim) {
     case 2: launch_instance<T, PROST_SPECTRAL_SINGULAR_NX2, 2>(p, il, grid, s); break;
     case 4: launch_instance<T, PROST_SPECTRAL_SINGULAR_NX2, 4>(p, il, grid, s); break;
@@ -201,5 +229,19 @@ int prost_hip_prox_spectral_f32(int op, int fn, float* res, const float* arg, co
 int prost_hip_prox_spectral_f64(int op, int fn, double* res, const double* arg, const double* tau_diag, double tau, const double* step_dev, const int* stop_dev,
                                 int invert_tau, size_t count, size_t dim, int interleaved, const double* const* coeff_ptr, const double* coeff_val, void* stream) {
   return launch_spectral<double>(op, fn, res, arg, tau_diag, tau, step_dev, stop_dev, invert_tau, count, dim, interleaved, coeff_ptr, coeff_val, stream);
+}
+int prost_hip_prox_eigen_nxn_plan(size_t n, int dtype, int* lanes_per_matrix, int* matrices_per_workgroup, size_t* lds_bytes) {
+  if (n < 1 || n > (size_t)prost::elemop::kEigenNxNMax) { set_error("prox_eigen_nxn_plan: n has to be in 1..32"); return 1; }
+  if (dtype != 0 && dtype != 1) { set_error("prox_eigen_nxn_plan: dtype is 0 (fp32) or 1 (fp64)"); return 1; }
+  int lanes = 1, matrices = kBlock;
+  size_t lds = (size_t)kBlock * n * n * (dtype == 0 ? sizeof(float) : sizeof(double));        // the tile of the interleaved layout
+  if ((int)n >= kEigenCoopMinN) {
+    const EigenCoopPlan g = eigen_coop_plan((int)n);
+    lanes = g.lanes; matrices = g.matrices; lds = g.lds_bytes;
+  }
+  if (lanes_per_matrix) *lanes_per_matrix = lanes;
+  if (matrices_per_workgroup) *matrices_per_workgroup = matrices;
+  if (lds_bytes) *lds_bytes = lds;
+  return 0;
 }
 }  // extern "C"

@@ -49,6 +49,41 @@ def sum_eigen_3x3(interleaved, fun, a=1, b=0, c=1, d=0, e=0, alpha=0, beta=0):
                                [count // 9, 9, bool(interleaved), coeffs]]
 
 
+def sum_eigen_nxn(n, interleaved, fun, a=1, b=0, c=1, d=0, e=0, alpha=0, beta=0):
+    """sum_eigen_nxn.m:1-26: h(lambda_1) + .. + h(lambda_n) of the symmetrised row-major n x n matrix a group of n * n values holds,
+    1 <= n <= 32"""
+    n = int(n)
+    if n < 1 or n > 32:
+        raise ValueError("n must be between 1 and 32")
+    coeffs = [_coeff(v) for v in (a, b, c, d, e, alpha, beta)]
+    return lambda idx, count: ["elem_operation:eigen_nxn:" + fun, idx, count, False,
+                               [count // (n * n), n * n, bool(interleaved), coeffs]]
+
+
+def sum_mass_norm(n, interleaved, cost=1):
+    """sum_mass_norm.m:1-21: cost times the mass norm of a 2-vector in R^n, n = 4 (6 components: the upper triangle of a skew-symmetric
+    matrix, row by row) or n = 5 (10 components).  cost: a scalar or one value per group.  The .m builder drops the cost for n = 5; here
+    a cost other than the scalar 1 is appended to the description and honoured."""
+    cost = _coeff(cost)
+    if n == 4:
+        return lambda idx, count: ["elem_operation:mass4", idx, count, False, [count // 6, 6, bool(interleaved), [cost]]]
+    if n == 5:
+        if cost.size == 1 and cost[0] == 1:
+            return lambda idx, count: ["elem_operation:mass5", idx, count, False, [count // 10, 10, bool(interleaved)]]
+        return lambda idx, count: ["elem_operation:mass5", idx, count, False, [count // 10, 10, bool(interleaved), [cost]]]
+    raise ValueError("Mass norm not implemented for n \\notin {4, 5}")
+
+
+def sum_ind_comass_ball(n, interleaved):
+    """sum_ind_comass_ball.m:1-18: indicator of the unit ball of the comass norm of a 2-vector in R^n, n = 4 or 5: the conjugate of
+    sum_mass_norm(n, interleaved)"""
+    if n == 4:
+        return lambda idx, count: ["elem_operation:ind_comass4_ball", idx, count, False, [count // 6, 6, bool(interleaved)]]
+    if n == 5:
+        return lambda idx, count: ["elem_operation:ind_comass5_ball", idx, count, False, [count // 10, 10, bool(interleaved)]]
+    raise ValueError("Indicator of comass norm ball not implemented for n \\notin {4, 5}")
+
+
 def conjugate(fun):
     def make(idx, count):
         child = fun(idx, count)
