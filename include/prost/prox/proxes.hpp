@@ -256,5 +256,33 @@ class ProxIndSum : public Prox<T> {
   T sum_, sum_2_;
 };
 
+/// projection onto the range of a sparse m x n matrix A with full column rank: x = A (A'A)^-1 A' y (prox_ind_range.cu).  The reference
+/// calls cuSPARSE and cuSOLVER (potrf at Initialize, potrs per evaluation); here the two products are prost_hip_csr_spmv_* on the stored
+/// transpose and on A, and the dense solve is prost_amd/csrc/kernels_prox_range.hip: a blocked Cholesky factorisation at Initialize (a
+/// pivot that is not positive throws there -- the reference ignores cuSOLVER's info), two blocked triangular sweeps per evaluation.
+/// The prox of an indicator does not depend on the step: tau, tau_diag and invert_tau are ignored.
+template <typename T>
+class ProxIndRange : public Prox<T> {
+ public:
+  ProxIndRange(size_t index, size_t size) : Prox<T>(index, size, false), nrows_(0), ncols_(0), nnz_(0), ready_(false) {}
+  /// A (m x n) in CSC, as the front end delivers it
+  void setA(int m, int n, int nnz, const std::vector<T>& val, const std::vector<int32_t>& ptr, const std::vector<int32_t>& ind);
+  /// AA = A'A, column-major; call after setA
+  void setAA(int m, int n, const std::vector<T>& val);
+  virtual void Initialize();
+  virtual void Release();
+  virtual size_t gpu_mem_amount() const;
+
+ protected:
+  virtual void EvalLocal(T*, T*, const T*, const T*, const T*, const T*, T tau, bool invert_tau);
+  size_t nrows_, ncols_, nnz_;
+  bool ready_;
+  std::vector<T> host_val_, host_val_t_, host_AA_;
+  std::vector<int32_t> host_ind_, host_ptr_, host_ind_t_, host_ptr_t_;
+  device_vector<T> val_, val_t_, L_, U_, dinv_, temp_;
+  device_vector<int32_t> ind_, ptr_, ind_t_, ptr_t_;
+  device_vector<double> workspace_;      // (bytes of prost_hip_range_potrs_workspace_bytes_*, rounded up to doubles)
+};
+
 }  // namespace prost
 #endif

@@ -339,6 +339,31 @@ int prost_hip_prox_spectral_f64(int op, int fn, double* res, const double* arg, 
  * (lanes * matrices = 256) and the LDS bytes of a workgroup (register path: the tile of the interleaved layout).  Any pointer may be
  * NULL.  Returns non-zero for any other n or dtype. */
 int prost_hip_prox_eigen_nxn_plan(size_t n, int dtype, int* lanes_per_matrix, int* matrices_per_workgroup, size_t* lds_bytes);
+/* The dense solve of ProxIndRange (additions; ABI version unchanged; kernels_prox_range.hip, arithmetic: prost/prox/potrs_blocks.hpp):
+ * x = A (A'A)^-1 A' y needs L L' z = t for the n x n matrix A'A, 1 <= n, n * n < 2^31.
+ * prost_hip_range_potrf_*: blocked Cholesky factorisation, run once.  In: L = A'A, column-major n x n (only its lower triangle is read).
+ * Out: L = the lower factor (upper triangle zero), U = L' (n x n), dinv = the inverted 64 x 64 diagonal blocks of L and their
+ * transposes (prost_hip_range_dinv_elements(n) values), *status_dev = -1, or the index of the first pivot that is not a positive finite
+ * number (L, U and dinv are then unspecified).  The arithmetic is fp64 for both data types.  workspace: prost_hip_range_potrf_workspace_bytes_*(n)
+ * bytes, 16-byte aligned.  No device sync, no allocation: the caller reads *status_dev back after synchronising the stream.
+ * prost_hip_range_potrs_*: v := (L L')^-1 v in place for one right-hand side, all arithmetic in T, no floating-point atomics, a fixed
+ * summation order (a repeated call repeats its bits); it does not allocate, copy or synchronise.  tier 0 = the plan's choice, 1 = small
+ * (one launch, one workgroup, the vector in LDS; the plan's choice up to n = 512 in fp32 and 320 in fp64, accepted up to n = 1024), 2 = large (one launch per block step of each sweep; workspace of
+ * prost_hip_range_potrs_workspace_bytes_*(n) bytes, 16-byte aligned; may be NULL on the small tier).  No workgroup waits for another
+ * inside a launch.
+ * prost_hip_range_potrs_plan: host only, no device needed, no launch.  For n and dtype (0 fp32, 1 fp64): the tier, the block size NB,
+ * the launches of one solve, the LDS bytes of a workgroup and the workspace bytes.  Any pointer may be NULL.  Non-zero for n = 0,
+ * n * n >= 2^31 or another dtype. */
+int prost_hip_range_potrs_plan(size_t n, int dtype, int* tier, int* nb, int* launches_per_solve, size_t* lds_bytes, size_t* workspace_bytes);
+size_t prost_hip_range_dinv_elements(size_t n);
+size_t prost_hip_range_potrf_workspace_bytes_f32(size_t n);
+size_t prost_hip_range_potrf_workspace_bytes_f64(size_t n);
+size_t prost_hip_range_potrs_workspace_bytes_f32(size_t n);
+size_t prost_hip_range_potrs_workspace_bytes_f64(size_t n);
+int prost_hip_range_potrf_f32(float* L, float* U, float* dinv, void* workspace, int* status_dev, size_t n, void* stream);
+int prost_hip_range_potrf_f64(double* L, double* U, double* dinv, void* workspace, int* status_dev, size_t n, void* stream);
+int prost_hip_range_potrs_f32(float* v, const float* L, const float* U, const float* dinv, void* workspace, size_t n, int tier, void* stream);
+int prost_hip_range_potrs_f64(double* v, const double* L, const double* U, const double* dinv, void* workspace, size_t n, int tier, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* PDHG building blocks, generic path (src/backend/backend_pdhg.cu)                            */

@@ -8,6 +8,7 @@
 #include <dlfcn.h>
 #include <iostream>
 #include <map>
+#include <memory>
 #include <sstream>
 
 #include "hipapi.hpp"
@@ -312,6 +313,23 @@ std::map<std::string, typename Factory<T>::ProxFactory>& Factory<T>::prox_reg() 
         return new ProxIndSum<T>(idx, size, count, dim, inds, sum, dim2 ? inds2.size() / dim2 : 0, dim2, inds2, (T)GetScalarFromCell(d, 5));
       }
       throw Exception("ind_sum: 3 or 6 data entries expected.");
+    };
+    reg["ind_range"] = [](size_t idx, size_t size, bool, const prost_value* d) -> Prox<T>* {       // factory.cpp:531-572; data cells { A, AA }
+      const prost_value* pa = cell_at(d, 0);
+      if (pa->kind != PROST_VALUE_SPARSE) throw Exception("Matrix A must be sparse!");
+      if (pa->rows != size) throw Exception("Matrix A does not fit size of the variable!");
+      const prost_value* paa = cell_at(d, 1);
+      if (paa->kind != PROST_VALUE_MATRIX) throw Exception("Matrix AA must be dense!");
+      if (pa->jc.size() != pa->cols + 1 || pa->jc[pa->cols] < 0 || (size_t)pa->jc[pa->cols] > pa->data.size() || (size_t)pa->jc[pa->cols] > pa->ir.size() ||
+          pa->rows > 0x7fffffff || pa->cols > 0x7fffffff || pa->jc[pa->cols] > 0x7fffffff)
+        throw Exception("ProxIndRange: the CSC arrays of 'A' do not fit its dimensions.");
+      if (paa->data.size() < paa->rows * paa->cols) throw Exception("ProxIndRange: the values of 'AA' do not fit its dimensions.");
+      const int nrows = (int)pa->rows, ncols = (int)pa->cols, nnz = (int)pa->jc[ncols];
+      std::unique_ptr<ProxIndRange<T>> prox(new ProxIndRange<T>(idx, size));
+      prox->setA(nrows, ncols, nnz, std::vector<T>(pa->data.begin(), pa->data.begin() + nnz), std::vector<int32_t>(pa->jc.begin(), pa->jc.end()),
+                 std::vector<int32_t>(pa->ir.begin(), pa->ir.begin() + nnz));
+      prox->setAA((int)paa->rows, (int)paa->cols, std::vector<T>(paa->data.begin(), paa->data.begin() + paa->rows * paa->cols));
+      return prox.release();
     };
     reg["ind_epi_quad"] = [](size_t idx, size_t, bool ds, const prost_value* d) -> Prox<T>* {
       const size_t count = (size_t)GetScalarFromCell(d, 0), dim = (size_t)GetScalarFromCell(d, 1);

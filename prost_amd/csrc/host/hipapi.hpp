@@ -34,6 +34,10 @@ template <typename T> struct Api;
     static constexpr auto prox_elem_moreau = prost_hip_prox_elem_moreau_##S;      \
     static constexpr auto prox_elem_arg = prost_hip_prox_elem_arg_##S;            \
     static constexpr auto prox_spectral = prost_hip_prox_spectral_##S;            \
+    static constexpr auto range_potrf = prost_hip_range_potrf_##S;                \
+    static constexpr auto range_potrs = prost_hip_range_potrs_##S;                \
+    static constexpr auto range_potrf_workspace_bytes = prost_hip_range_potrf_workspace_bytes_##S; \
+    static constexpr auto range_potrs_workspace_bytes = prost_hip_range_potrs_workspace_bytes_##S; \
     static constexpr auto prox_epi_quad = prost_hip_prox_epi_quad_##S;            \
     static constexpr auto prox_elem_ind_sum = prost_hip_prox_elem_ind_sum_##S;    \
     static constexpr auto prox_elem_ind_simplex = prost_hip_prox_elem_ind_simplex_##S; \

@@ -439,4 +439,83 @@ void ProxIndSum<T>::EvalLocal(T* res, T*, const T* arg, const T*, const T* tau_d
 template class ProxIndSum<float>;
 template class ProxIndSum<double>;
 
+// ---- range of a sparse matrix ----
+template <typename T>
+void ProxIndRange<T>::setA(int m, int n, int nnz, const std::vector<T>& val, const std::vector<int32_t>& ptr, const std::vector<int32_t>& ind) {
+  if (m < 0 || n < 0 || nnz < 0 || ptr.size() != (size_t)n + 1 || val.size() < (size_t)nnz || ind.size() < (size_t)nnz)
+    throw Exception("ProxIndRange: the CSC arrays of 'A' do not fit its dimensions.");
+  if (ptr[0] != 0 || ptr[n] != nnz) throw Exception("ProxIndRange: the CSC arrays of 'A' do not fit its dimensions.");
+  for (int c = 0; c < n; c++)
+    if (ptr[c + 1] < ptr[c]) throw Exception("ProxIndRange: the column starts of 'A' decrease.");
+  for (int k = 0; k < nnz; k++)                      // unchecked in the reference; a row index outside A would read out of bounds on the device
+    if (ind[k] < 0 || ind[k] >= m) throw Exception("ProxIndRange: 'A' has a row index outside [0, rows).");
+  nrows_ = m; ncols_ = n; nnz_ = nnz;
+  // the CSC arrays of A are the CSR arrays of A'; A itself in CSR comes from one transposition (as BlockSparse::CreateFromCSC)
+  host_ind_t_ = ind; host_ptr_t_ = ptr; host_val_t_ = val;
+  host_ind_.assign(nnz_, 0); host_val_.assign(nnz_, (T)0); host_ptr_.assign(nrows_ + 1, 0);
+  csr2csc<T>(n, m, nnz, host_val_t_.data(), host_ind_t_.data(), host_ptr_t_.data(), host_val_.data(), host_ind_.data(), host_ptr_.data());
+}
+template <typename T>
+void ProxIndRange<T>::setAA(int m, int n, const std::vector<T>& val) {
+  if (m != n) throw Exception("ProxIndRange: Matrix 'AA' must be square!");
+  if ((size_t)m != ncols_) throw Exception("ProxIndRange: Matrix 'AA' must fit dimension of 'A'!");
+  if (val.size() != (size_t)m * (size_t)n) throw Exception("ProxIndRange: the values of 'AA' do not fit its dimensions.");
+  host_AA_ = val;
+}
+template <typename T>
+void ProxIndRange<T>::Initialize() {
+  const size_t n = ncols_;
+  if (n < 1 || host_AA_.size() != n * n) throw Exception("ProxIndRange: 'A' and 'AA' have to be set before Initialize().");
+  size_t solve_ws = 0;
+  if (prost_hip_range_potrs_plan(n, dtype_id<T>(), nullptr, nullptr, nullptr, nullptr, &solve_ws) != 0)
+    throw Exception("ProxIndRange: 'AA' is n x n with n * n >= 2^31: too large for the dense solve.");
+  ready_ = false;
+  val_ = host_val_; ind_ = host_ind_; ptr_ = host_ptr_;
+  val_t_ = host_val_t_; ind_t_ = host_ind_t_; ptr_t_ = host_ptr_t_;
+  L_ = host_AA_;
+  U_.resize(n * n);
+  dinv_.resize(prost_hip_range_dinv_elements(n));
+  temp_.resize(n);
+  device_vector<double> setup_ws((Api<T>::range_potrf_workspace_bytes(n) + sizeof(double) - 1) / sizeof(double));
+  device_vector<int32_t> status(1);
+  void* s = CurrentStream();
+  CheckHip(Api<T>::range_potrf(L_.data(), U_.data(), dinv_.data(), setup_ws.data(), reinterpret_cast<int*>(status.data()), n, s), "range_potrf");
+  std::vector<int32_t> info;
+  status.copy_to(info);                              // synchronous: the one read-back of the set-up
+  CheckHip(prost_hip_check_last_error(), "range_potrf kernels");
+  if (info[0] >= 0) {
+    Release();
+    std::stringstream ss;
+    ss << "ProxIndRange: matrix 'AA' is not positive definite (pivot " << info[0] << ").";
+    throw Exception(ss.str());
+  }
+  workspace_.resize((solve_ws + sizeof(double) - 1) / sizeof(double));
+  ready_ = true;
+}
+template <typename T>
+void ProxIndRange<T>::Release() {
+  ready_ = false;
+  val_.clear(); ind_.clear(); ptr_.clear(); val_t_.clear(); ind_t_.clear(); ptr_t_.clear();
+  L_.clear(); U_.clear(); dinv_.clear(); temp_.clear(); workspace_.clear();
+}
+template <typename T>
+size_t ProxIndRange<T>::gpu_mem_amount() const {
+  const size_t n = ncols_;
+  size_t solve_ws = 0;
+  if (n >= 1) prost_hip_range_potrs_plan(n, dtype_id<T>(), nullptr, nullptr, nullptr, nullptr, &solve_ws);
+  // A and A' in CSR, L and U, the inverted diagonal blocks, the n-vector between the products and the workspace of the solve
+  return 2 * nnz_ * (sizeof(T) + sizeof(int32_t)) + (nrows_ + 1 + n + 1) * sizeof(int32_t) + (2 * n * n + prost_hip_range_dinv_elements(n) + n) * sizeof(T) + solve_ws;
+}
+template <typename T>
+void ProxIndRange<T>::EvalLocal(T* res, T*, const T* arg, const T*, const T*, const T*, T, bool) {
+  if (!ready_) throw Exception("ProxIndRange used before Initialize().");
+  void* s = CurrentStream();
+  // t = A' y consumes the argument before anything is written: res may be arg
+  CheckHip(Api<T>::csr_spmv(temp_.data(), arg, ncols_, nnz_, val_t_.data(), ptr_t_.data(), ind_t_.data(), s), "csr_spmv");
+  CheckHip(Api<T>::range_potrs(temp_.data(), L_.data(), U_.data(), dinv_.data(), workspace_.data(), ncols_, 0, s), "range_potrs");
+  CheckHip(Api<T>::csr_spmv(res, temp_.data(), nrows_, nnz_, val_.data(), ptr_.data(), ind_.data(), s), "csr_spmv");
+}
+template class ProxIndRange<float>;
+template class ProxIndRange<double>;
+
 }  // namespace prost

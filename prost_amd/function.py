@@ -153,3 +153,16 @@ def sum_ind_sum2(dim, inds, s1, dim2=None, inds2=None, s2=None):
         return lambda idx, count: ["ind_sum", idx, count, True, [int(dim), inds, float(s1)]]
     inds2 = np.asarray(inds2, dtype=np.int64).ravel()
     return lambda idx, count: ["ind_sum", idx, count, True, [int(dim), inds, float(s1), int(dim2), inds2, float(s2)]]
+
+
+def ind_range(A, AA=None):
+    """ind_range.m:1-11: indicator of the range of the sparse m x n matrix A (full column rank); its prox is the projection
+    x = A (A'A)^-1 A' y.  AA = A'A as a full matrix (computed here when left out).  A sparse AA is handed on as it is: the factory
+    answers "Matrix AA must be dense!"."""
+    import scipy.sparse as sp
+    A = sp.csc_matrix(A, dtype=np.float64, copy=True)
+    if AA is None:
+        AA = (A.T @ A).toarray()
+    if not sp.issparse(AA):
+        AA = np.array(AA, dtype=np.float64, copy=True)
+    return lambda idx, count: ["ind_range", idx, count, False, [A, AA]]
