@@ -8,6 +8,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "batch_rcp.hpp"
 #include "prost/prox/elemop/function_1d.hpp"
 #include "prost_hip.h"
 
@@ -133,8 +134,10 @@ __device__ __forceinline__ void div_to_float_exact_vec(const double (&x)[VEC], c
 // ~2^-52, q = (float)((double)n * r).  |n r - n/d| < 2^-51 |n/d|, while the exact quotient of two
 // 24-bit floats is never within 2^-49 (relative) of a float rounding boundary (n = m d with m a
 // 25-bit midpoint is impossible, and n - m d is a non-zero multiple of the product's last place),
-// so rounding n r gives RN(n/d) -- including subnormal quotients and signed zeros; d = +-0, +-inf
-// or NaN are NOT supported (callers substitute / fall back).
+// so rounding n r gives RN(n/d) -- including subnormal quotients and signed zeros, EXCEPT a subnormal quotient
+// that is exactly a tie (n = m d has solutions there): r is exact for a power-of-two d, which rounds those ties
+// like the division, and not otherwise (batch_rcp.hpp, "Why that suffices").  d = +-0, +-inf or NaN are NOT
+// supported (callers substitute / fall back).
 __device__ __forceinline__ double rcp_refined(float d) {
   const double dd = (double)d;
   double r = __builtin_amdgcn_rcp(dd);                     // v_rcp_f64: 2^-23 relative
@@ -145,18 +148,20 @@ __device__ __forceinline__ double rcp_refined(float d) {
   return r;
 }
 __device__ __forceinline__ double rcp_refined(double d) { return 1.0 / d; }
-// the same from the single-precision reciprocal estimate (v_rcp_f32, 1 ulp, converted) instead of v_rcp_f64: two Newton
-// steps take 2^-22.4 to below 2^-52 all the same
-__device__ __forceinline__ double rcp_refined_s(float d) {
-  const double dd = (double)d;
-  double r = (double)__builtin_amdgcn_rcpf(d);
-  double e = __builtin_fma(-dd, r, 1.0);
-  r = __builtin_fma(r, e, r);
-  e = __builtin_fma(-dd, r, 1.0);
-  r = __builtin_fma(r, e, r);
-  return r;
+// the refined reciprocals of the VEC divisors of one lane, two of them from one v_rcp_f64 (batch_rcp.hpp: error bounds and the
+// rounding argument are there); an odd last one gets its own.  Divisors in [2^-48, 2^63].  (Four per seed, rcp_refined4, saves
+// three seeds of four but holds four more double registers across the Newton steps: the paired two-iterations kernel, at
+// exactly 128 VGPRs, spills with it -- docs/rounds/r13.md.  No kernel uses it.)
+struct RcpSeedF64 {
+  __device__ __forceinline__ double operator()(double p) const { return __builtin_amdgcn_rcp(p); }
+};
+template <int VEC>
+__device__ __forceinline__ void rcp_refined_pairs(const float (&d)[VEC], double (&r)[VEC]) {
+  constexpr int P = VEC / 2 * 2;
+#pragma unroll
+  for (int j = 0; j < P; j += 2) rcp_refined2(d[j], d[j + 1], RcpSeedF64(), r[j], r[j + 1]);
+  if constexpr (P < VEC) r[P] = rcp_refined(d[P]);
 }
-__device__ __forceinline__ double rcp_refined_s(double d) { return 1.0 / d; }
 __device__ __forceinline__ float mul_rcp(float n, double r) { return (float)((double)n * r); }
 // mul_rcp(n, r) with the quotient of a zero numerator forced to +0, in one instruction less than "+ 0.0f" afterwards:
 // fma(n, r, +0.0) rounds exactly like the product and turns a -0 product (n = +-0) into +0 already in double.  (A
@@ -167,8 +172,9 @@ __device__ __forceinline__ double mul_rcp_pz(double n, double r) { return n * r 
 __device__ __forceinline__ float min0(float t) { return __builtin_fminf(t, 0.0f); }
 __device__ __forceinline__ double min0(double t) { return t > 0.0 ? 0.0 : t; }
 // ---- tolerance-class arithmetic (prost_hip_fused_desc.arith = PROST_HIP_ARITH_FMAD) -----------------------
-// one instruction each: v_min_f32 / v_max_f32 (operands are never NaN where these are used) and v_rsq_f32 (1 ulp; +inf for +0,
-// which the callers' min(b * rsq, 1) turns into the factor 1 on a zero vector)
+// one instruction each: v_min_f32 / v_max_f32 (fmin / fmax: a NaN operand is dropped; the tolerance class never has one, and
+// norm2_leq0_fast, the one user in the exact class, relies on exactly that) and v_rsq_f32 (1 ulp; +inf for +0, which the callers'
+// min(b * rsq, 1) turns into the factor 1 on a zero vector)
 __device__ __forceinline__ float t_min(float a, float b) { return __builtin_fminf(a, b); }
 __device__ __forceinline__ float t_max(float a, float b) { return __builtin_fmaxf(a, b); }
 __device__ __forceinline__ double t_min(double a, double b) { return __builtin_fmin(a, b); }
@@ -204,32 +210,6 @@ template <> struct SharedDivisor<double> {
   __device__ __forceinline__ explicit SharedDivisor(double d_) : d(d_), y(rcp_newton2(d_)), mid(f64_mid(d_)) {}
   __device__ __forceinline__ double div(double n) const { return (mid && (f64_mid(n) || n == 0.0)) ? div_mid(n, d, y) : n / d; }
 };
-// ---- the same quotient in single precision only -------------------------------------------------
-// fp64 instructions and the f32 <-> f64 conversions issue at half the fp32 rate on this part (16 vs 32 lanes per
-// cycle and SIMD), v_rcp_f64 far below that; the double-reciprocal form above spends ~70 of its issue cycles there.
-// This is the compiler's own IEEE expansion of `/` (v_rcp_f32, one Newton step on the reciprocal, quotient estimate,
-// two residual corrections) WITHOUT its v_div_scale / v_div_fmas / v_div_fixup range handling: identical bits whenever
-// that handling would be the identity -- d and 1/d normal, the quotient not subnormal, exponent(n) - exponent(d) < 96,
-// |n| >= 2^-103 -- and for n = +-0 (result +0: the callers want the sign of a zero quotient dropped).  Callers keep
-// d in [2^-48, 2^63] and check the QUOTIENT: |q| >= 2^-55 implies |n| >= 2^-103 and a normal quotient.
-struct RcpF32 { float d, y; };
-__device__ __forceinline__ RcpF32 rcp_f32_newton(float d) {
-  RcpF32 r;
-  r.d = d;
-  const float y0 = __builtin_amdgcn_rcpf(d);
-  const float e = __builtin_fmaf(-d, y0, 1.0f);
-  r.y = __builtin_fmaf(e, y0, y0);
-  return r;
-}
-__device__ __forceinline__ float div_f32_unscaled(float n, const RcpF32& r) {
-  const float q0 = n * r.y;
-  const float r0 = __builtin_fmaf(-r.d, q0, n);
-  const float q1 = __builtin_fmaf(r0, r.y, q0);
-  const float r1 = __builtin_fmaf(-r.d, q1, n);
-  return __builtin_fmaf(r1, r.y, q1);
-}
-constexpr float kDivF32MinQuotient = 2.7755575615628914e-17f;      // 2^-55
-
 // sqrtf(x) for x in [2^-96, 2^126]: v_sqrt_f32 (1 ulp) + the compiler's own +-1 ulp residual test,
 // without the 2^32 range scaling and the zero / infinity fix-up that the general expansion carries
 __device__ __forceinline__ float sqrt_midrange(float x) {
@@ -259,20 +239,24 @@ __device__ __forceinline__ double sqrt_midrange(double x) {
 // function_1d.hpp:75-87) on the NC gradient components of VEC pixels:
 //     out_i = pr v_i / ||v||,  pr = min(||v|| - b, 0) + b;   ||v|| = 0 -> 0
 // nv = the squared norms as the reference accumulates them, av = the components.  Norms up to 2^126 take the short
-// correctly rounded forms above (sqrt without range scaling, ONE refined double reciprocal per pixel, the products
-// rounded through fma(n, r, +0) so that zero quotients come out as +0).  A zero norm runs the same code with
+// correctly rounded forms above (sqrt without range scaling, the refined double reciprocals of two pixels of the lane from ONE
+// seed -- SHARE = false: one per pixel, for instances whose registers do not allow it --, the products rounded through fma(n, r, +0) so that zero quotients come out as +0).  A zero norm runs the same code with
 // ||v|| := 2^-48: then pr = RN(RN(2^-48 - b) + b) = 0 for every radius b >= 2^-20, the numerators are +-0 and the
 // results +0, the value the reference writes.  The same holds for non-zero norms below 2^-96 (squares of
 // subnormal-range components): the reference computes pr = 0 and quotients +-0 there as well, so with
 // `tiny_is_zero` (= b >= 2^-20, wave-uniform) they need no separate path; results are equal in value to the
 // reference's, zeros may differ in sign.  Without it such norms, like norms above 2^126 and NaNs, take the general
 // expansions.
-template <class T, int NC, int VEC>
+template <class T, int NC, int VEC, bool SHARE = true>
 __device__ __forceinline__ void norm2_leq0_fast(const T (&nv)[VEC], const T (&av)[NC][VEC], T b, bool tiny_is_zero, T (&out)[NC][VEC]) {
   constexpr float kLo = 1.2621774483536189e-29f;             // 2^-96
+  constexpr bool kShare = SHARE && sizeof(T) == 4 && VEC > 1;      // else: the code as it was, one reciprocal per pixel
   T nmax = 0;
 #pragma unroll
-  for (int j = 0; j < VEC; j++) nmax = nv[j] > nmax ? nv[j] : nmax;
+  for (int j = 0; j < VEC; j++) {
+    if constexpr (kShare) nmax = t_max(nmax, nv[j]);      // v_max3_f32 per two values; a NaN leaves nmax as it is, like the select
+    else nmax = nv[j] > nmax ? nv[j] : nmax;
+  }
   bool mid = sizeof(T) == 4 && nmax <= (T)8.507059173023462e37f;
   if (!tiny_is_zero) {
     unsigned tmin = 0xFFFFFFFFu;
@@ -281,13 +265,28 @@ __device__ __forceinline__ void norm2_leq0_fast(const T (&nv)[VEC], const T (&av
     mid = mid && tmin >= (unsigned)__float_as_int(kLo) - 1u;
   }
   if (__builtin_expect(mid, 1)) {
+    if constexpr (kShare) {
+      // all norms first, then their reciprocals (one seed per two), then the quotients
+      float nrm[VEC];
+      double r[VEC];
 #pragma unroll
-    for (int j = 0; j < VEC; j++) {
-      const T nrm = sqrt_midrange(nv[j] > (T)kLo ? nv[j] : (T)kLo);
-      const T pr = min0(nrm - b) + b;
-      const auto r = rcp_refined(nrm);
+      for (int j = 0; j < VEC; j++) nrm[j] = sqrt_midrange(nv[j] > (T)kLo ? nv[j] : (T)kLo);
+      rcp_refined_pairs<VEC>(nrm, r);
 #pragma unroll
-      for (int i = 0; i < NC; i++) out[i][j] = mul_rcp_pz(pr * av[i][j], r);
+      for (int j = 0; j < VEC; j++) {
+        const T pr = min0(nrm[j] - b) + b;
+#pragma unroll
+        for (int i = 0; i < NC; i++) out[i][j] = mul_rcp_pz(pr * av[i][j], r[j]);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < VEC; j++) {
+        const T nrm = sqrt_midrange(nv[j] > (T)kLo ? nv[j] : (T)kLo);
+        const T pr = min0(nrm - b) + b;
+        const auto r = rcp_refined(nrm);
+#pragma unroll
+        for (int i = 0; i < NC; i++) out[i][j] = mul_rcp_pz(pr * av[i][j], r);
+      }
     }
   } else {
     if constexpr (sizeof(T) == 8) {

@@ -321,7 +321,11 @@ __global__ void __launch_bounds__(kWave, (RES && VART && FAST && LCH == 1) ? 3 :
       if constexpr (FAST) {
         // out = pr v / ||v||, pr = min(||v|| - b, 0) + b, 0 for ||v|| = 0: device_math.hpp
         if constexpr (kFM) norm2_moreau_post<T, FFN, kFM ? 2 * LCH : 1, kFM ? VEC : 1>(nv, vv, av, sigS, a.f_val, uf, out);
-        else norm2_leq0_fast<T, 2 * LCH, VEC>(nv, av, a.f_val[1], tiny_is_zero, out);
+        else {
+          // (the variable-Tau instance with residual sums spills 12 bytes; sharing reciprocal seeds would make it 36: docs/rounds/r13.md)
+          constexpr bool kShareRcp = !(VART && RES && !RAG);
+          norm2_leq0_fast<T, 2 * LCH, VEC, kShareRcp>(nv, av, a.f_val[1], tiny_is_zero, out);
+        }
       }
       if (RES && c >= a.rx0 && c < a.rx1) {                // primal_residual_transform (backend_pdhg.cu:97-120)
 #pragma unroll

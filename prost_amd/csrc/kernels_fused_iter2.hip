@@ -375,7 +375,11 @@ __global__ void __launch_bounds__(PAIR ? 2 * kWave : kWave, FAST ? (PF == 0 ? ((
       if constexpr (!FMAD) {
         T out[2][VEC];
         if constexpr (kFM) norm2_moreau_post<T, FFN, kFM ? 2 : 1, kFM ? VEC : 1>(nv, vv, av, sigS, a.f_val, P.uf, out);
-        else norm2_leq0_fast<T, 2, VEC>(nv, av, a.f_val[1], tiny_is_zero, out);
+        else {
+          // (the plain PF = 3 instances sit at 168 VGPRs and spill; shared reciprocal seeds cost two of them more scratch: docs/rounds/r13.md)
+          constexpr bool kShareRcp = !(PF == 3 && MODE == 0);
+          norm2_leq0_fast<T, 2, VEC, kShareRcp>(nv, av, a.f_val[1], tiny_is_zero, out);
+        }
 #pragma unroll
         for (int j = 0; j < VEC; j++) { o1[j] = out[0][j]; o2[j] = out[1][j]; }
       }

@@ -238,7 +238,9 @@ __global__ void __launch_bounds__(kWave, WAVES)
         norm += arg2 * arg2;
         av[0][j] = arg1; av[1][j] = arg2; nv[j] = norm;
       }
-      norm2_leq0_fast<T, 2, VEC>(nv, av, bq, tiny_is_zero, out);
+      // (the K = 2 instances with residual sums sit at 168 VGPRs and spill; shared reciprocal seeds cost one of them more scratch: docs/rounds/r13.md)
+      constexpr bool kShareRcp = !(K == 2 && RES);
+      norm2_leq0_fast<T, 2, VEC, kShareRcp>(nv, av, bq, tiny_is_zero, out);
 #pragma unroll
       for (int j = 0; j < VEC; j++) { o1[j] = out[0][j]; o2[j] = out[1][j]; }
       if (RES && acc) {             // the tolerance-compared sums: fp32 with fused multiply-adds, as in the pair kernel's straight-line instances
