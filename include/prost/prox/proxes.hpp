@@ -284,5 +284,34 @@ class ProxIndRange : public Prox<T> {
   device_vector<double> workspace_;      // (bytes of prost_hip_range_potrs_workspace_bytes_*, rounded up to doubles)
 };
 
+/// projection onto the epigraphs of max-affine functions, { (x, y) | y >= max_i <a_i, x> - b_i } per group of dim = d + 1 values
+/// (x_1 .. x_d, y): the function behind prost.function.sum_ind_epi_polyhedral, which the reference's users add from outside its tree.
+/// Group g owns the count_vec[g] constraints that start at index_vec[g] (0-based, counted in constraints; lists may be shared, the
+/// starts need not be monotone); the d coefficients of one constraint are adjacent in a.  2 <= dim <= 4.  Every argument is checked
+/// at construction (messages name the prox).  The kernel (prost_amd/csrc/kernels_prox_epi_polyhedral.hip, arithmetic in
+/// prost/prox/epi_polyhedral.hpp) is a dual active-set projection with a hard step cap; fallback_count() reads back how many groups
+/// reached it since Initialize.  The prox of an indicator does not depend on the step: tau, tau_diag and invert_tau are ignored.
+template <typename T>
+class ProxIndEpiPolyhedral : public ProxSeparableSum<T> {
+ public:
+  ProxIndEpiPolyhedral(size_t index, size_t count, size_t dim, bool interleaved, const std::vector<T>& a, const std::vector<T>& b,
+                       const std::vector<double>& count_vec, const std::vector<double>& index_vec);
+  virtual void Initialize();
+  virtual void Release();
+  virtual size_t gpu_mem_amount() const { return (a_.size() + b_.size()) * sizeof(T) + (cnt_.size() + idx_.size() + 1) * sizeof(int32_t); }
+  size_t max_count() const { return max_count_; }
+  /// groups that reached the step cap since Initialize (synchronous read-back)
+  size_t fallback_count() const;
+
+ protected:
+  virtual void EvalLocal(T*, T*, const T*, const T*, const T*, const T*, T tau, bool invert_tau);
+  std::vector<T> a_, b_;
+  std::vector<int32_t> cnt_, idx_;
+  size_t max_count_;
+  bool ready_;
+  device_vector<T> d_a_, d_b_;
+  device_vector<int32_t> d_cnt_, d_idx_, d_fallback_;
+};
+
 }  // namespace prost
 #endif

@@ -364,6 +364,24 @@ int prost_hip_range_potrf_f32(float* L, float* U, float* dinv, void* workspace, 
 int prost_hip_range_potrf_f64(double* L, double* U, double* dinv, void* workspace, int* status_dev, size_t n, void* stream);
 int prost_hip_range_potrs_f32(float* v, const float* L, const float* U, const float* dinv, void* workspace, size_t n, int tier, void* stream);
 int prost_hip_range_potrs_f64(double* v, const double* L, const double* U, const double* dinv, void* workspace, size_t n, int tier, void* stream);
+/* ProxIndEpiPolyhedral (additions; ABI version unchanged; kernels_prox_epi_polyhedral.hip, arithmetic: prost/prox/epi_polyhedral.hpp):
+ * per group g < count the projection of z = (x_1 .. x_d, y), d = dim - 1, onto { y >= max_i <a_i, x> - b_i }, i running over the
+ * cnt[g] constraints that start at idx[g] (0-based, counted in constraints; lists may be shared or overlap, idx need not be
+ * monotone).  a: the d coefficients of one constraint adjacent; b: one value per constraint.  Element j of group g lies at
+ * g + count * j (planar) or g * dim + j (interleaved); res may be arg.  2 <= dim <= 4, count < 2^31.  max_count: an upper bound of
+ * cnt[] (the prox passes the largest entry): it fixes the lanes per group, and a larger cnt[g] is clamped to it, so the work of a
+ * launch is bounded whatever cnt holds.  Every idx[g] + cnt[g] has to stay within b: the caller checks that (ProxIndEpiPolyhedral
+ * does at creation).  A group stops after step_cap_a * (cnt[g] + dim) + step_cap_b steps, writes the feasible point
+ * (x0, max(y0, max_i <a_i, x0> - b_i)) and adds 1 to *fallback_counter (a device counter, may be NULL).  No allocation, copy or
+ * synchronisation.
+ * prost_hip_epi_polyhedral_plan: host only, no device needed, no launch.  For max_count, dim and dtype (0 fp32, 1 fp64): the lanes
+ * that share a group (a power of two <= 64, non-decreasing in max_count) and the two constants of the step cap.  Any pointer may be
+ * NULL.  Non-zero for another dim or dtype or max_count >= 2^31. */
+int prost_hip_epi_polyhedral_plan(size_t max_count, size_t dim, int dtype, int* lanes_per_group, int* step_cap_a, int* step_cap_b);
+int prost_hip_prox_ind_epi_polyhedral_f32(float* res, const float* arg, size_t count, size_t dim, int interleaved, const float* a, const float* b,
+                                          const int32_t* cnt, const int32_t* idx, size_t max_count, unsigned* fallback_counter, void* stream);
+int prost_hip_prox_ind_epi_polyhedral_f64(double* res, const double* arg, size_t count, size_t dim, int interleaved, const double* a, const double* b,
+                                          const int32_t* cnt, const int32_t* idx, size_t max_count, unsigned* fallback_counter, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* PDHG building blocks, generic path (src/backend/backend_pdhg.cu)                            */

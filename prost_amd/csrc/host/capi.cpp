@@ -2,6 +2,7 @@
 // (the MEX gateway of the reference, matlab/+prost/private/{prost,factory}.cpp, without mex.h).
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -330,6 +331,29 @@ std::map<std::string, typename Factory<T>::ProxFactory>& Factory<T>::prox_reg() 
                  std::vector<int32_t>(pa->ir.begin(), pa->ir.begin() + nnz));
       prox->setAA((int)paa->rows, (int)paa->cols, std::vector<T>(paa->data.begin(), paa->data.begin() + paa->rows * paa->cols));
       return prox.release();
+    };
+    reg["ind_epi_polyhedral"] = [](size_t idx, size_t size, bool, const prost_value* d) -> Prox<T>* {   // data cells { count, dim, interleaved, { a, b, count_vec, index_vec } }
+      const double cd = GetScalarFromCell(d, 0), dd = GetScalarFromCell(d, 1);
+      if (!(dd >= 2) || !(dd <= 4) || dd != std::floor(dd)) {
+        std::stringstream ss;
+        ss << "ProxIndEpiPolyhedral: dim = " << dd << " is not supported, dim has to be between 2 and 4.";
+        throw Exception(ss.str());
+      }
+      const size_t count = cd > 0 ? (size_t)cd : 0, dim = (size_t)dd;
+      if (count * dim != size) {
+        std::stringstream ss;
+        ss << "ProxIndEpiPolyhedral: size = " << size << " is not count * dim = " << count << " * " << dim << ".";
+        throw Exception(ss.str());
+      }
+      const bool interleaved = GetScalarFromCell(d, 2) > 0.;
+      const prost_value* co = cell_at(d, 3);
+      auto vec = [](const prost_value* v, const char* what) {      // an empty vector is a value here (no constraints at all)
+        if (!v || v->kind != PROST_VALUE_MATRIX) throw Exception(std::string("ProxIndEpiPolyhedral: ") + what + " has to be a vector of type single or double.");
+        return std::vector<double>(v->data.begin(), v->data.end());
+      };
+      const std::vector<double> a = vec(cell_at(co, 0), "a"), b = vec(cell_at(co, 1), "b");
+      return new ProxIndEpiPolyhedral<T>(idx, count, dim, interleaved, std::vector<T>(a.begin(), a.end()), std::vector<T>(b.begin(), b.end()),
+                                         vec(cell_at(co, 2), "count_vec"), vec(cell_at(co, 3), "index_vec"));
     };
     reg["ind_epi_quad"] = [](size_t idx, size_t, bool ds, const prost_value* d) -> Prox<T>* {
       const size_t count = (size_t)GetScalarFromCell(d, 0), dim = (size_t)GetScalarFromCell(d, 1);

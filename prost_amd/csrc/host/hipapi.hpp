@@ -39,6 +39,7 @@ template <typename T> struct Api;
     static constexpr auto range_potrf_workspace_bytes = prost_hip_range_potrf_workspace_bytes_##S; \
     static constexpr auto range_potrs_workspace_bytes = prost_hip_range_potrs_workspace_bytes_##S; \
     static constexpr auto prox_epi_quad = prost_hip_prox_epi_quad_##S;            \
+    static constexpr auto prox_ind_epi_polyhedral = prost_hip_prox_ind_epi_polyhedral_##S; \
     static constexpr auto prox_elem_ind_sum = prost_hip_prox_elem_ind_sum_##S;    \
     static constexpr auto prox_elem_ind_simplex = prost_hip_prox_elem_ind_simplex_##S; \
     static constexpr auto transform_prescale = prost_hip_transform_prescale_##S;  \

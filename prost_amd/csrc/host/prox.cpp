@@ -1,6 +1,7 @@
 // prox.cpp -- proximal operators of the prost host library (calls prost_hip.h only).
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <sstream>
 
 #include "hipapi.hpp"
@@ -517,5 +518,73 @@ void ProxIndRange<T>::EvalLocal(T* res, T*, const T* arg, const T*, const T*, co
 }
 template class ProxIndRange<float>;
 template class ProxIndRange<double>;
+
+// ---- epigraph of a max-affine function ----
+template <typename T>
+ProxIndEpiPolyhedral<T>::ProxIndEpiPolyhedral(size_t index, size_t count, size_t dim, bool interleaved, const std::vector<T>& a, const std::vector<T>& b,
+                                              const std::vector<double>& count_vec, const std::vector<double>& index_vec)
+    : ProxSeparableSum<T>(index, count, dim, interleaved, false), a_(a), b_(b), max_count_(0), ready_(false) {
+  const size_t lim = (size_t)1 << 31;
+  if (dim < 2 || dim > 4) {
+    std::stringstream ss;
+    ss << "ProxIndEpiPolyhedral: dim = " << dim << " is not supported, dim has to be between 2 and 4.";
+    throw Exception(ss.str());
+  }
+  if (count_vec.size() != count || index_vec.size() != count) {
+    std::stringstream ss;
+    ss << "ProxIndEpiPolyhedral: count_vec and index_vec need one entry per group (count = " << count << ", got " << count_vec.size() << " and " << index_vec.size() << ").";
+    throw Exception(ss.str());
+  }
+  if (a.size() != b.size() * (dim - 1)) {
+    std::stringstream ss;
+    ss << "ProxIndEpiPolyhedral: a has " << a.size() << " entries, expected len(b) * (dim - 1) = " << b.size() * (dim - 1) << ".";
+    throw Exception(ss.str());
+  }
+  if (count >= lim || b.size() >= lim || a.size() >= lim) throw Exception("ProxIndEpiPolyhedral: the number of groups, of constraints and of coefficients each have to stay below 2^31.");
+  cnt_.resize(count); idx_.resize(count);
+  for (size_t g = 0; g < count; g++) {
+    const double c = count_vec[g], s = index_vec[g];
+    if (!(c >= 0) || !(s >= 0) || c != std::floor(c) || s != std::floor(s) || c >= (double)lim || s >= (double)lim) {
+      std::stringstream ss;
+      ss << "ProxIndEpiPolyhedral: count_vec and index_vec have to hold non-negative integers below 2^31 (group " << g << ").";
+      throw Exception(ss.str());
+    }
+    if ((size_t)c + (size_t)s > b.size()) {
+      std::stringstream ss;
+      ss << "ProxIndEpiPolyhedral: group " << g << " names constraints " << (size_t)s << " .. " << (size_t)s + (size_t)c << ", but there are only " << b.size() << ".";
+      throw Exception(ss.str());
+    }
+    cnt_[g] = (int32_t)c; idx_[g] = (int32_t)s;
+    if ((size_t)c > max_count_) max_count_ = (size_t)c;
+  }
+}
+template <typename T>
+void ProxIndEpiPolyhedral<T>::Initialize() {
+  ready_ = false;
+  d_a_ = a_; d_b_ = b_; d_cnt_ = cnt_; d_idx_ = idx_;
+  d_fallback_.resize(1);
+  ready_ = true;
+}
+template <typename T>
+void ProxIndEpiPolyhedral<T>::Release() {
+  ready_ = false;
+  d_a_.clear(); d_b_.clear(); d_cnt_.clear(); d_idx_.clear(); d_fallback_.clear();
+}
+template <typename T>
+size_t ProxIndEpiPolyhedral<T>::fallback_count() const {
+  if (!ready_) return 0;
+  std::vector<int32_t> v;
+  d_fallback_.copy_to(v);
+  return (size_t)(uint32_t)v[0];
+}
+template <typename T>
+void ProxIndEpiPolyhedral<T>::EvalLocal(T* res, T*, const T* arg, const T*, const T*, const T*, T, bool) {
+  if (!ready_) throw Exception("ProxIndEpiPolyhedral used before Initialize().");
+  CheckHip(Api<T>::prox_ind_epi_polyhedral(res, arg, this->count_, this->dim_, this->interleaved_ ? 1 : 0, d_a_.data(), d_b_.data(), d_cnt_.data(), d_idx_.data(),
+                                           max_count_, reinterpret_cast<unsigned*>(d_fallback_.data()), CurrentStream()),
+           "prox_ind_epi_polyhedral");
+}
+template class ProxIndEpiPolyhedral<float>;
+template class ProxIndEpiPolyhedral<double>;
 
 }  // namespace prost

@@ -166,3 +166,15 @@ def ind_range(A, AA=None):
     if not sp.issparse(AA):
         AA = np.array(AA, dtype=np.float64, copy=True)
     return lambda idx, count: ["ind_range", idx, count, False, [A, AA]]
+
+
+def sum_ind_epi_polyhedral(dim, interleaved, a, b, count_vec, index_vec):
+    """sum_ind_epi_polyhedral(dim, interleaved, a, b, count_vec, index_vec): indicator of the epigraphs y >= max_i <a_i, x> - b_i per
+    group (x_1 .. x_{dim-1}, y), 2 <= dim <= 4.  Group g owns the count_vec[g] constraints that start at index_vec[g] (0-based,
+    counted in constraints; groups may share a list, the starts need not be monotone).  a: the dim - 1 coefficients of one constraint
+    adjacent, len(a) = len(b) * (dim - 1).  Its prox is the projection onto the epigraph."""
+    def vec(v):
+        return np.asarray(v, dtype=np.float64).ravel()
+    coeffs = [vec(a), vec(b), vec(count_vec), vec(index_vec)]
+    return lambda idx, count: ["ind_epi_polyhedral", idx, count, False,
+                               [count // dim, dim, bool(interleaved), coeffs]]
