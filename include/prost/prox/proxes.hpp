@@ -88,6 +88,8 @@ class ProxMoreau : public Prox<T> {
   virtual void get_separable_structure(std::vector<std::tuple<size_t, size_t, size_t>>& sep) { conjugate_->get_separable_structure(sep); }
   virtual bool supports_arg_source() const;
   virtual bool takes_step_record() const { return supports_arg_source(); }
+  /// true for a conjugated ProxIndEpiConjQuad1D: the inner prox does not depend on the step, the two scaling passes read it on the device
+  virtual bool takes_step_view() const;
   virtual bool supports_op_source() const { return supports_arg_source() && conjugate_->supports_op_source(); }
   /// the wrapped operation's description with `moreau` set (a wrap of a wrap is not described)
   virtual bool describe(ProxDesc& d) const;
@@ -97,6 +99,7 @@ class ProxMoreau : public Prox<T> {
 
  protected:
   virtual void EvalLocal(T*, T*, const T*, const T*, const T*, const T*, T tau, bool invert_tau);
+  virtual void EvalLocalStepView(T*, T*, const T*, const T*, const T*, const T*, const typename Prox<T>::StepView& view, bool invert_tau);
   shared_ptr<Prox<T>> conjugate_;
   device_vector<T> scaled_arg_;
 };
@@ -311,6 +314,35 @@ class ProxIndEpiPolyhedral : public ProxSeparableSum<T> {
   bool ready_;
   device_vector<T> d_a_, d_b_;
   device_vector<int32_t> d_cnt_, d_idx_, d_fallback_;
+};
+
+/// projection onto the epigraphs of conjugate quadratic pieces, { (y, t) | t >= phi*(y) } per group of dim = 2 values (y, t), with
+/// phi(x) = a x^2 + b x + c on [alpha, beta] and +inf elsewhere: the function behind prost.function.sum_ind_epi_conjquad_1d (the
+/// sublabel-accurate relaxation with piecewise quadratic data terms), which the reference's users add from outside its tree.  Each
+/// coefficient holds 1 or count values.  a >= 0, alpha <= beta, everything finite but alpha = -inf / beta = +inf with a > 0 (that ray
+/// is absent); checked at construction (messages name the prox).  The kernel (prost_amd/csrc/kernels_prox_epi_conjquad.hip, arithmetic
+/// in prost/prox/epi_conjquad.hpp) runs a Newton loop with a hard step cap in the arc region; fallback_count() reads back how many
+/// groups reached it since Initialize.  The prox of an indicator does not depend on the step: tau, tau_diag and invert_tau are
+/// ignored, and under a device-resident step-size rule (Prox::StepView) only the stop word is read.
+template <typename T>
+class ProxIndEpiConjQuad1D : public ProxSeparableSum<T> {
+ public:
+  ProxIndEpiConjQuad1D(size_t index, size_t size, size_t count, bool interleaved, const std::array<std::vector<T>, 5>& coeffs);
+  virtual void Initialize();
+  virtual void Release();
+  virtual size_t gpu_mem_amount() const;
+  virtual bool takes_step_view() const { return true; }
+  /// groups that reached the step cap since Initialize (synchronous read-back)
+  size_t fallback_count() const;
+
+ protected:
+  virtual void EvalLocal(T*, T*, const T*, const T*, const T*, const T*, T tau, bool invert_tau);
+  virtual void EvalLocalStepView(T*, T*, const T*, const T*, const T*, const T*, const typename Prox<T>::StepView& view, bool invert_tau);
+  void Launch(T* res, const T* arg, const int* stop);
+  std::array<std::vector<T>, 5> coeffs_;       // a, b, c, alpha, beta
+  std::array<device_vector<T>, 5> d_coeffs_;
+  device_vector<int32_t> d_fallback_;
+  bool ready_;
 };
 
 }  // namespace prost

@@ -382,6 +382,32 @@ int prost_hip_prox_ind_epi_polyhedral_f32(float* res, const float* arg, size_t c
                                           const int32_t* cnt, const int32_t* idx, size_t max_count, unsigned* fallback_counter, void* stream);
 int prost_hip_prox_ind_epi_polyhedral_f64(double* res, const double* arg, size_t count, size_t dim, int interleaved, const double* a, const double* b,
                                           const int32_t* cnt, const int32_t* idx, size_t max_count, unsigned* fallback_counter, void* stream);
+/* ProxIndEpiConjQuad1D (additions; ABI version unchanged; kernels_prox_epi_conjquad.hip, arithmetic: prost/prox/epi_conjquad.hpp):
+ * per group g < count the projection of (y, t) onto { t >= phi*(y) }, phi* the conjugate of phi(x) = a x^2 + b x + c on [alpha, beta]
+ * (+inf elsewhere), a >= 0, alpha <= beta: a left ray of slope alpha, an arc, a right ray of slope beta.  alpha = -inf / beta = +inf
+ * are allowed for a > 0 (that ray is absent).  y lies at g and t at g + count (planar), or (y, t) at 2 g, 2 g + 1 (interleaved; read
+ * as one 8 / 16-byte access per lane when res and arg are both aligned for it, element by element otherwise); res may be arg.  Each of
+ * the five coefficients is a device pointer to count values, or NULL with the value passed as a double.  The caller checks the
+ * coefficients (ProxIndEpiConjQuad1D does at creation).  The Newton loop of the arc stops after the step cap; a group that gets there
+ * writes the feasible point (y0, max(t0, phi*(y0))) and adds 1 to *fallback_counter (a device counter, may be NULL).  stop_dev: NULL,
+ * or the stop word of a device-resident step-size rule (prost_hip_pdhg_record_view): non-zero when the kernel runs makes it return
+ * without writing.  The prox does not depend on a step size.  No allocation, copy or synchronisation.
+ * prost_hip_epi_conjquad_step_cap: host only, no device needed, no launch: the step cap of dtype (0 fp32, 1 fp64); non-zero for
+ * another dtype. */
+int prost_hip_epi_conjquad_step_cap(int dtype, int* cap);
+/* The scaling passes of ProxMoreau with the step size read on the device (additions; kernels_prox_moreau_view.hip): the arithmetic of
+ * prost_hip_moreau_prescale_* / _postscale_* with tau = *step_dev when the kernel runs; a non-zero *stop_dev makes them return without
+ * writing (both pointers are required).  For a conjugated prox that does not depend on the step itself. */
+int prost_hip_moreau_prescale_view_f32(float* o, const float* a, const float* td, const float* step_dev, const int* stop_dev, int inv, size_t n, void* s);
+int prost_hip_moreau_prescale_view_f64(double* o, const double* a, const double* td, const double* step_dev, const int* stop_dev, int inv, size_t n, void* s);
+int prost_hip_moreau_postscale_view_f32(float* r, const float* a, const float* td, const float* step_dev, const int* stop_dev, int inv, size_t n, void* s);
+int prost_hip_moreau_postscale_view_f64(double* r, const double* a, const double* td, const double* step_dev, const int* stop_dev, int inv, size_t n, void* s);
+int prost_hip_prox_ind_epi_conjquad_1d_f32(float* res, const float* arg, size_t count, int interleaved, const float* a_ptr, double a_val, const float* b_ptr,
+                                           double b_val, const float* c_ptr, double c_val, const float* alpha_ptr, double alpha_val, const float* beta_ptr,
+                                           double beta_val, unsigned* fallback_counter, const int* stop_dev, void* stream);
+int prost_hip_prox_ind_epi_conjquad_1d_f64(double* res, const double* arg, size_t count, int interleaved, const double* a_ptr, double a_val, const double* b_ptr,
+                                           double b_val, const double* c_ptr, double c_val, const double* alpha_ptr, double alpha_val, const double* beta_ptr,
+                                           double beta_val, unsigned* fallback_counter, const int* stop_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* PDHG building blocks, generic path (src/backend/backend_pdhg.cu)                            */

@@ -355,6 +355,25 @@ std::map<std::string, typename Factory<T>::ProxFactory>& Factory<T>::prox_reg() 
       return new ProxIndEpiPolyhedral<T>(idx, count, dim, interleaved, std::vector<T>(a.begin(), a.end()), std::vector<T>(b.begin(), b.end()),
                                          vec(cell_at(co, 2), "count_vec"), vec(cell_at(co, 3), "index_vec"));
     };
+    reg["ind_epi_conjquad_1d"] = [](size_t idx, size_t size, bool, const prost_value* d) -> Prox<T>* {   // data cells { count, 2, interleaved, { a, b, c, alpha, beta } }
+      const double cd = GetScalarFromCell(d, 0), dd = GetScalarFromCell(d, 1);
+      if (dd != 2) {
+        std::stringstream ss;
+        ss << "ProxIndEpiConjQuad1D: dim = " << dd << " is not supported, a group is (y, t): dim has to be 2.";
+        throw Exception(ss.str());
+      }
+      const size_t count = cd > 0 ? (size_t)cd : 0;
+      const bool interleaved = GetScalarFromCell(d, 2) > 0.;
+      const prost_value* co = cell_at(d, 3);
+      static const char* const names[5] = {"a", "b", "c", "alpha", "beta"};
+      std::array<std::vector<T>, 5> coeffs;
+      for (int i = 0; i < 5; i++) {
+        const prost_value* v = cell_at(co, i);
+        if (!v || v->kind != PROST_VALUE_MATRIX) throw Exception(std::string("ProxIndEpiConjQuad1D: ") + names[i] + " has to be a scalar or a vector of type single or double.");
+        coeffs[i].assign(v->data.begin(), v->data.end());
+      }
+      return new ProxIndEpiConjQuad1D<T>(idx, size, count, interleaved, coeffs);
+    };
     reg["ind_epi_quad"] = [](size_t idx, size_t, bool ds, const prost_value* d) -> Prox<T>* {
       const size_t count = (size_t)GetScalarFromCell(d, 0), dim = (size_t)GetScalarFromCell(d, 1);
       const bool interleaved = GetScalarFromCell(d, 2) > 0.;

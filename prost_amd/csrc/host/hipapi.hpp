@@ -40,6 +40,9 @@ template <typename T> struct Api;
     static constexpr auto range_potrs_workspace_bytes = prost_hip_range_potrs_workspace_bytes_##S; \
     static constexpr auto prox_epi_quad = prost_hip_prox_epi_quad_##S;            \
     static constexpr auto prox_ind_epi_polyhedral = prost_hip_prox_ind_epi_polyhedral_##S; \
+    static constexpr auto prox_ind_epi_conjquad_1d = prost_hip_prox_ind_epi_conjquad_1d_##S; \
+    static constexpr auto moreau_prescale_view = prost_hip_moreau_prescale_view_##S; \
+    static constexpr auto moreau_postscale_view = prost_hip_moreau_postscale_view_##S; \
     static constexpr auto prox_elem_ind_sum = prost_hip_prox_elem_ind_sum_##S;    \
     static constexpr auto prox_elem_ind_simplex = prost_hip_prox_elem_ind_simplex_##S; \
     static constexpr auto transform_prescale = prost_hip_transform_prescale_##S;  \

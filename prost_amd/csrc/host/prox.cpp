@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <limits>
 #include <sstream>
 
 #include "hipapi.hpp"
@@ -230,6 +231,16 @@ void ProxMoreau<T>::EvalLocal(T* res, T* res_end, const T* arg, const T* arg_end
   conjugate_->EvalLocal(res, res_end, scaled_arg_.data(), scaled_arg_.data() + n, tau_diag, tau_end, tau, !invert_tau);
   CheckHip(Api<T>::moreau_postscale(res, arg, tau_diag, (double)tau, invert_tau ? 1 : 0, n, CurrentStream()), "moreau_postscale");
   (void)arg_end;
+}
+template <typename T>
+bool ProxMoreau<T>::takes_step_view() const { return dynamic_cast<ProxIndEpiConjQuad1D<T>*>(conjugate_.get()) != nullptr; }
+template <typename T>
+void ProxMoreau<T>::EvalLocalStepView(T* res, T* res_end, const T* arg, const T*, const T* tau_diag, const T* tau_end, const typename Prox<T>::StepView& view, bool invert_tau) {
+  if (!takes_step_view()) throw Exception("ProxMoreau: only a conjugated prox that does not depend on the step takes it from the device.");
+  const size_t n = this->size_;
+  CheckHip(Api<T>::moreau_prescale_view(scaled_arg_.data(), arg, tau_diag, view.step, view.stop, invert_tau ? 1 : 0, n, CurrentStream()), "moreau_prescale_view");
+  conjugate_->EvalLocalStepView(res, res_end, scaled_arg_.data(), scaled_arg_.data() + n, tau_diag, tau_end, view, !invert_tau);
+  CheckHip(Api<T>::moreau_postscale_view(res, arg, tau_diag, view.step, view.stop, invert_tau ? 1 : 0, n, CurrentStream()), "moreau_postscale_view");
 }
 template <typename T>
 bool ProxMoreau<T>::describe(ProxDesc& d) const {
@@ -586,5 +597,88 @@ void ProxIndEpiPolyhedral<T>::EvalLocal(T* res, T*, const T* arg, const T*, cons
 }
 template class ProxIndEpiPolyhedral<float>;
 template class ProxIndEpiPolyhedral<double>;
+
+// ---- epigraph of the conjugate of a quadratic piece ----
+template <typename T>
+ProxIndEpiConjQuad1D<T>::ProxIndEpiConjQuad1D(size_t index, size_t size, size_t count, bool interleaved, const std::array<std::vector<T>, 5>& coeffs)
+    : ProxSeparableSum<T>(index, count, 2, interleaved, false), coeffs_(coeffs), ready_(false) {
+  static const char* const names[5] = {"a", "b", "c", "alpha", "beta"};
+  if (size != 2 * count) {
+    std::stringstream ss;
+    ss << "ProxIndEpiConjQuad1D: size = " << size << " is not 2 * count = 2 * " << count << ".";
+    throw Exception(ss.str());
+  }
+  for (int i = 0; i < 5; i++)
+    if (coeffs_[i].size() != 1 && coeffs_[i].size() != count) {
+      std::stringstream ss;
+      ss << "ProxIndEpiConjQuad1D: coefficient " << names[i] << " has " << coeffs_[i].size() << " entries, expected 1 or count = " << count << ".";
+      throw Exception(ss.str());
+    }
+  auto at = [this](int i, size_t g) { return coeffs_[i].size() == 1 ? coeffs_[i][0] : coeffs_[i][g]; };
+  size_t groups = 1;
+  for (int i = 0; i < 5; i++) groups = std::max(groups, coeffs_[i].size());
+  for (size_t g = 0; g < groups; g++) {
+    const T a = at(0, g), b = at(1, g), c = at(2, g), alpha = at(3, g), beta = at(4, g);
+    std::stringstream ss;
+    if (!std::isfinite(a) || !std::isfinite(b) || !std::isfinite(c)) ss << "a, b and c have to be finite";
+    else if (std::isnan(alpha) || std::isnan(beta) || alpha == std::numeric_limits<T>::infinity() || beta == -std::numeric_limits<T>::infinity())
+      ss << "alpha has to be finite or -inf and beta finite or +inf";
+    else if (a < 0) ss << "a = " << a << " is negative, the piece has to be convex";
+    else if (alpha > beta) ss << "alpha = " << alpha << " is above beta = " << beta;
+    else if (a == 0 && (std::isinf(alpha) || std::isinf(beta))) ss << "a = 0 needs finite alpha and beta";
+    if (!ss.str().empty()) {
+      std::stringstream msg;
+      msg << "ProxIndEpiConjQuad1D: " << ss.str() << " (group " << g << ").";
+      throw Exception(msg.str());
+    }
+  }
+}
+template <typename T>
+void ProxIndEpiConjQuad1D<T>::Initialize() {
+  ready_ = false;
+  for (int i = 0; i < 5; i++)
+    if (coeffs_[i].size() > 1) d_coeffs_[i] = coeffs_[i];
+  d_fallback_.resize(1);
+  ready_ = true;
+}
+template <typename T>
+void ProxIndEpiConjQuad1D<T>::Release() {
+  ready_ = false;
+  for (int i = 0; i < 5; i++) d_coeffs_[i].clear();
+  d_fallback_.clear();
+}
+template <typename T>
+size_t ProxIndEpiConjQuad1D<T>::gpu_mem_amount() const {
+  size_t mem = sizeof(int32_t);
+  for (int i = 0; i < 5; i++) if (coeffs_[i].size() > 1) mem += coeffs_[i].size() * sizeof(T);
+  return mem;
+}
+template <typename T>
+size_t ProxIndEpiConjQuad1D<T>::fallback_count() const {
+  if (!ready_) return 0;
+  std::vector<int32_t> v;
+  d_fallback_.copy_to(v);
+  return (size_t)(uint32_t)v[0];
+}
+template <typename T>
+void ProxIndEpiConjQuad1D<T>::Launch(T* res, const T* arg, const int* stop) {
+  if (!ready_) throw Exception("ProxIndEpiConjQuad1D used before Initialize().");
+  const T* ptr[5]; double val[5];
+  for (int i = 0; i < 5; i++) {
+    const bool vec = coeffs_[i].size() > 1;
+    ptr[i] = vec ? d_coeffs_[i].data() : nullptr; val[i] = vec ? 0.0 : (double)coeffs_[i][0];
+  }
+  CheckHip(Api<T>::prox_ind_epi_conjquad_1d(res, arg, this->count_, this->interleaved_ ? 1 : 0, ptr[0], val[0], ptr[1], val[1], ptr[2], val[2], ptr[3], val[3],
+                                            ptr[4], val[4], reinterpret_cast<unsigned*>(d_fallback_.data()), stop, CurrentStream()),
+           "prox_ind_epi_conjquad_1d");
+}
+template <typename T>
+void ProxIndEpiConjQuad1D<T>::EvalLocal(T* res, T*, const T* arg, const T*, const T*, const T*, T, bool) { Launch(res, arg, nullptr); }
+template <typename T>
+void ProxIndEpiConjQuad1D<T>::EvalLocalStepView(T* res, T*, const T* arg, const T*, const T*, const T*, const typename Prox<T>::StepView& view, bool) {
+  Launch(res, arg, view.stop);
+}
+template class ProxIndEpiConjQuad1D<float>;
+template class ProxIndEpiConjQuad1D<double>;
 
 }  // namespace prost

@@ -178,3 +178,13 @@ def sum_ind_epi_polyhedral(dim, interleaved, a, b, count_vec, index_vec):
     coeffs = [vec(a), vec(b), vec(count_vec), vec(index_vec)]
     return lambda idx, count: ["ind_epi_polyhedral", idx, count, False,
                                [count // dim, dim, bool(interleaved), coeffs]]
+
+
+def sum_ind_epi_conjquad_1d(interleaved, a, b, c, alpha, beta):
+    """sum_ind_epi_conjquad_1d(interleaved, a, b, c, alpha, beta): indicator of the epigraphs t >= phi*(y) per group (y, t), phi* the
+    conjugate of phi(x) = a x^2 + b x + c on [alpha, beta] (+inf elsewhere): a left ray of slope alpha, an arc, a right ray of slope
+    beta.  Each coefficient is a scalar or one value per group; a >= 0, alpha <= beta; alpha = -inf / beta = +inf are allowed for
+    a > 0.  Its prox is the projection onto the epigraph."""
+    coeffs = [np.asarray(v, dtype=np.float64).ravel() for v in (a, b, c, alpha, beta)]
+    return lambda idx, count: ["ind_epi_conjquad_1d", idx, count, False,
+                               [count // 2, 2, bool(interleaved), coeffs]]
