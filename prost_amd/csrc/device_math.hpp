@@ -172,9 +172,9 @@ __device__ __forceinline__ double mul_rcp_pz(double n, double r) { return n * r 
 __device__ __forceinline__ float min0(float t) { return __builtin_fminf(t, 0.0f); }
 __device__ __forceinline__ double min0(double t) { return t > 0.0 ? 0.0 : t; }
 // ---- tolerance-class arithmetic (prost_hip_fused_desc.arith = PROST_HIP_ARITH_FMAD) -----------------------
-// one instruction each: v_min_f32 / v_max_f32 (fmin / fmax: a NaN operand is dropped; the tolerance class never has one, and
-// norm2_leq0_fast, the one user in the exact class, relies on exactly that) and v_rsq_f32 (1 ulp; +inf for +0, which the callers'
-// min(b * rsq, 1) turns into the factor 1 on a zero vector)
+// one instruction each: v_min_f32 / v_max_f32 (fmin / fmax: a NaN operand is dropped; the tolerance class never has one, and the
+// exact class does not use them: norm2_leq0_fast compares bit patterns so that a NaN is seen) and v_rsq_f32 (1 ulp; +inf for +0,
+// which the callers' min(b * rsq, 1) turns into the factor 1 on a zero vector)
 __device__ __forceinline__ float t_min(float a, float b) { return __builtin_fminf(a, b); }
 __device__ __forceinline__ float t_max(float a, float b) { return __builtin_fmaxf(a, b); }
 __device__ __forceinline__ double t_min(double a, double b) { return __builtin_fmin(a, b); }
@@ -251,13 +251,16 @@ template <class T, int NC, int VEC, bool SHARE = true>
 __device__ __forceinline__ void norm2_leq0_fast(const T (&nv)[VEC], const T (&av)[NC][VEC], T b, bool tiny_is_zero, T (&out)[NC][VEC]) {
   constexpr float kLo = 1.2621774483536189e-29f;             // 2^-96
   constexpr bool kShare = SHARE && sizeof(T) == 4 && VEC > 1;      // else: the code as it was, one reciprocal per pixel
-  T nmax = 0;
+  // The largest squared norm of the lane, compared as BIT PATTERNS: a squared norm is >= +0 or NaN, unsigned integers order the
+  // patterns of such values like the values themselves, and every NaN (of either sign) lies above +inf, hence above 2^126.  A float
+  // maximum would drop a NaN (v_max_f32 and a select both do) and keep its lane on the short forms, which turn it into 0 * NaN = NaN
+  // where the reference's `norm > 0` writes 0.  Same instruction count: v_max3_u32 per two values, one unsigned compare.
+  unsigned nmax = 0;
+  if constexpr (sizeof(T) == 4) {
 #pragma unroll
-  for (int j = 0; j < VEC; j++) {
-    if constexpr (kShare) nmax = t_max(nmax, nv[j]);      // v_max3_f32 per two values; a NaN leaves nmax as it is, like the select
-    else nmax = nv[j] > nmax ? nv[j] : nmax;
+    for (int j = 0; j < VEC; j++) nmax = max(nmax, (unsigned)__float_as_int((float)nv[j]));
   }
-  bool mid = sizeof(T) == 4 && nmax <= (T)8.507059173023462e37f;
+  bool mid = sizeof(T) == 4 && nmax <= 0x7E800000u;                // 2^126
   if (!tiny_is_zero) {
     unsigned tmin = 0xFFFFFFFFu;
 #pragma unroll

@@ -150,11 +150,31 @@ def live():
     np.savez_compressed(os.path.join(OUT, "live_reference.npz"), **out)
 
 
+def edges():
+    """the reference's answers on the directed operands of tests/elem_edge_cases.py (branch thresholds, special values), compared by
+    tests/test_elementwise_edges.py: one digest per case (answer_digest, 32 bytes), the Function1DLq answers as values"""
+    sys.path.insert(0, os.path.dirname(OUT))
+    import elem_edge_cases as E
+    import test_oracle_pinning as t
+    out, names, digests = {}, [], []
+    for dt in (np.float32, np.float64):
+        for name, args in E.cases(dt):
+            r = ref.prox_elem(*args)
+            if args[1] == "lq":
+                out[name] = r
+            else:
+                names.append(name)
+                digests.append(bytes.fromhex(t.answer_digest(r)))
+    out["digest_keys"] = np.array(names, dtype="S")
+    out["digests"] = np.frombuffer(b"".join(digests), dtype=np.uint8).reshape(len(names), 32)
+    np.savez_compressed(os.path.join(OUT, "elementwise_edges.npz"), **out)
+
+
 if __name__ == "__main__":
     assert ref.available() or ref.build(), "oracle/_ref is not built and /root/reference is absent"
-    which = sys.argv[1:] or ["elementwise", "pdhg", "pdhg64", "misc", "live"]
+    which = sys.argv[1:] or ["elementwise", "pdhg", "pdhg64", "misc", "live", "edges"]
     for name in which:
-        {"elementwise": elementwise, "pdhg": pdhg, "pdhg64": pdhg64, "misc": misc, "live": live}[name]()
+        {"elementwise": elementwise, "pdhg": pdhg, "pdhg64": pdhg64, "misc": misc, "live": live, "edges": edges}[name]()
     for fn in sorted(os.listdir(OUT)):
         if fn.endswith(".npz"):
             print(fn, os.path.getsize(os.path.join(OUT, fn)) // 1024, "KiB")

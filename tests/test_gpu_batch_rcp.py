@@ -17,13 +17,12 @@ import pytest
 
 import oracle
 import prost_amd as prost
+from pdhg_iteration_reference import F_COEFFS, SVAL, oracle_iteration
 from prost_amd import synthetic
 
 pytestmark = pytest.mark.gpu
 
 DT = np.float32
-F_COEFFS = [1.0, 1.0, 1.0, 0.0, 0.0, 0.3, 0.0]
-SVAL = 0.5
 TAUS, SIGMAS, THETAS = (0.9, 0.7), (1.1, 1.4), (0.85, 0.8)
 HUGE = 1.3 * 2.0 ** 60
 SHAPES = [(nx, ny) for nx in (5, 19, 37) for ny in (8, 248, 252)]
@@ -56,26 +55,6 @@ def patterned(nx, ny, planes, comps, huge_comps, rng, huge_row=3):
         else:
             y[huge_comps, :, r + 1] = HUGE
     return x.reshape(-1).astype(DT), f.reshape(-1).astype(DT), y.reshape(-1).astype(DT), m
-
-
-def oracle_iteration(kind, x, y, shape, g_coeffs, tval, tau, sigma, theta):
-    """one PDHG iteration as the reference evaluates it (backend_pdhg.cu:313-370), every operation rounded to fp32; also returns
-    the squared norms of the dual prox's arguments"""
-    nx, ny, L = shape
-    n = nx * ny * L
-    grad = oracle.grad3d if kind == "3d" else oracle.grad2d
-    comps = 3 if kind == "3d" else 2
-    tau, sigma, theta = DT(tau), DT(sigma), DT(theta)
-    Td, Sd = np.full(n, tval, DT), np.full(comps * n, SVAL, DT)
-    kty = grad(y, nx, ny, L, adjoint=True)
-    x1 = oracle.prox_elem(0, "square", (x - tau * Td * kty).astype(DT), Td, tau, n, 1, False, g_coeffs)
-    kx, kxp = grad(x1, nx, ny, L), grad(x, nx, ny, L)
-    arg = (y + sigma * Sd * ((1 + theta) * kx - theta * kxp)).astype(DT)
-    count, dim = (n, 3) if kind == "3d" else (nx * ny, 2 * L)
-    y1 = oracle.prox_elem(1, "ind_leq0", arg, Sd, sigma, count, dim, False, F_COEFFS)
-    with np.errstate(over="ignore"):
-        nv = (arg.astype(np.float64).reshape(dim, count) ** 2).sum(axis=0)
-    return x1, y1, nv
 
 
 def fused_desc(hip, kind, shape, g_coeffs, tval):
