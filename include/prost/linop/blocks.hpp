@@ -202,6 +202,41 @@ class BlockKronDense : public Block<T> {
   device_vector<T> data_;
 };
 
+/// the coupling of the sublabel-accurate data term (Moellenhoff et al., CVPR 2016; the reference's CustomSources.cmake.example names
+/// block_dataterm_sublabel and ships no source): L equidistant labels on [left, right], k = L - 1 intervals, N = nx ny pixels, domain
+/// [u ; w] and range [r ; s] of 2 N k values each in planes of N (element (p, i) at i N + p), applied without a matrix.  Arithmetic:
+/// prost/linop/dataterm_sublabel.hpp.  No describe(): the block runs on the generic paths.
+template <typename T>
+class BlockDatatermSublabel : public Block<T> {
+ public:
+  /// checks every argument (messages start with "BlockDatatermSublabel: "); declared_rows / declared_cols < 0: no size was declared
+  static BlockDatatermSublabel<T>* Create(size_t row, size_t col, double nx, double ny, double L, double left, double right,
+                                          double declared_rows = -1, double declared_cols = -1);
+  virtual void Initialize();
+  virtual void Release();
+  virtual T row_sum(size_t row, T alpha) const;
+  virtual T col_sum(size_t col, T alpha) const;
+  virtual void row_sums(T* out, T alpha) const;              ///< one constant per plane
+  virtual void col_sums(T* out, T alpha) const;
+  virtual size_t gpu_mem_amount() const { return gamma_.size() * sizeof(T); }
+  size_t npixels() const { return npixels_; }
+  size_t labels() const { return L_; }
+  T delta() const { return delta_; }
+  const std::vector<T>& gamma() const { return gamma_; }
+
+ protected:
+  BlockDatatermSublabel(size_t row, size_t col, size_t npixels, size_t L, double left, double right);
+  virtual void EvalLocalAdd(T*, T*, const T*, const T*);
+  virtual void EvalAdjointLocalAdd(T*, T*, const T*, const T*);
+  virtual void EvalLocal(T*, T*, const T*, const T*);
+  virtual void EvalAdjointLocal(T*, T*, const T*, const T*);
+  void Product(T* r, const T* x, bool transpose, bool acc);
+  size_t npixels_, L_;
+  T delta_;
+  std::vector<T> gamma_;          ///< gamma_i = left + i delta, i < L - 1 (formed in double, rounded to T)
+  device_vector<T> d_gamma_;
+};
+
 /// constant-coefficient multi-diagonal block; `identity` maps here (block_diags.hpp, identity.m:11-12)
 template <typename T>
 class BlockDiags : public Block<T> {

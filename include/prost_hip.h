@@ -191,6 +191,20 @@ int prost_hip_dense_gemv_acc_f64(double* res, const double* rhs, size_t nrows, s
 int prost_hip_dense_gemv_f32(float* res, const float* rhs, size_t nrows, size_t ncols, const float* data, int transpose, void* workspace, void* stream);
 int prost_hip_dense_gemv_f64(double* res, const double* rhs, size_t nrows, size_t ncols, const double* data, int transpose, void* workspace, void* stream);
 size_t prost_hip_dense_gemv_workspace_bytes(size_t nrows, size_t ncols);
+/* BlockDatatermSublabel (additions; ABI version unchanged; kernels_linop_dataterm_sublabel.hip, arithmetic and order of operations:
+ * prost/linop/dataterm_sublabel.hpp): the coupling of the sublabel-accurate data term for L >= 2 equidistant labels, k = L - 1
+ * intervals, npixels pixels, every part k planes of npixels values (element (p, i) at i * npixels + p).  transpose == 0:
+ * res = [r ; s] from rhs = [u ; w], r_i = (delta u_i + gamma_i w_i) - delta sum_{j > i} w_j, s_i = -w_i; transpose != 0:
+ * res = [u ; w] from rhs = [r ; s], u_i = delta r_i, w_i = (gamma_i r_i - s_i) - delta sum_{j < i} r_j.  accumulate != 0 stores
+ * res + value instead of value.  res and rhs hold 2 * npixels * (L - 1) values each; gamma: L - 1 values of T in device memory; delta
+ * is already rounded to T.  Any alignment of T is accepted: 16-byte aligned res and rhs with npixels a multiple of 4 (fp32) / 2 (fp64)
+ * move one 16-byte access per lane and plane, everything else one element.  Aliasing: res == rhs (the same pointer) is allowed, in
+ * both directions and with accumulate (a lane reads plane i before it writes plane i and touches no other pixel); any other overlap
+ * of the two ranges is not, and gamma overlaps neither (it is read through the scalar cache).  No atomics: a call repeats its bits.  No allocation, copy or synchronisation. */
+int prost_hip_linop_dataterm_sublabel_f32(float* res, const float* rhs, size_t npixels, size_t L, const float* gamma, double delta, int transpose, int accumulate,
+                                          void* stream);
+int prost_hip_linop_dataterm_sublabel_f64(double* res, const double* rhs, size_t npixels, size_t L, const double* gamma, double delta, int transpose, int accumulate,
+                                          void* stream);
 /* x = beta * x (beta == 0 -> zero fill): thrust::fill / transform at linearoperator.cu:140-147 */
 /* x[i] = value (thrust::fill, linearoperator.cu:140-147; also used for preconditioners that are one constant: the
  * gradient blocks' row / column sums are, block_gradient2d.cu:154-163, so nothing is uploaded for them) */

@@ -81,6 +81,31 @@ def id_kron_dense(K, diaglength):
     return _kron_dense("id_kron_dense", K, diaglength)
 
 
+def dataterm_sublabel(nx, ny, L, left, right):
+    """The coupling of the sublabel-accurate data term (Moellenhoff et al., CVPR 2016) for L equidistant labels on [left, right],
+    applied without a matrix.  k = L - 1 intervals, N = nx ny pixels, every part k planes of N values (element (p, i) at i N + p, the
+    layout of gradient2d(nx, ny, k), sum_ind_simplex(k, False) and sum_ind_epi_conjquad_1d(False, ..)).  Domain [u ; w]: the lifted
+    labelling and the interval weights; range [r ; s]: (r_i, s_i) lives in the epigraph of the conjugate of piece i
+    (alpha = left + i delta, beta = alpha + delta, delta = (right - left) / (L - 1)).  Per pixel
+    r_i = delta u_i + gamma_i w_i - delta sum_{j > i} w_j and s_i = -w_i."""
+    for name, v in (("nx", nx), ("ny", ny), ("L", L)):
+        if isinstance(v, bool) or not np.isfinite(v) or int(v) != v:
+            raise ValueError("dataterm_sublabel: %s = %r is not an integer" % (name, v))
+    nx, ny, L, left, right = int(nx), int(ny), int(L), float(left), float(right)
+    if L < 2:
+        raise ValueError("dataterm_sublabel: L = %d labels, at least 2 are needed" % L)
+    if nx < 1 or ny < 1:
+        raise ValueError("dataterm_sublabel: nx = %d and ny = %d have to be at least 1" % (nx, ny))
+    if not (np.isfinite(left) and np.isfinite(right)):
+        raise ValueError("dataterm_sublabel: the bounds left = %r and right = %r have to be finite" % (left, right))
+    if not left < right:
+        raise ValueError("dataterm_sublabel: left = %r has to be below right = %r" % (left, right))
+    n = 2 * nx * ny * (L - 1)
+    sz = [n, n]
+    data = [nx, ny, L, left, right]
+    return lambda row, col, nrows, ncols: [["dataterm_sublabel", row, col, data], sz]
+
+
 def diags(nrows, ncols, factors, offsets):
     sz = [nrows, ncols]
     data = [nrows, ncols, np.atleast_1d(np.asarray(factors, dtype=np.float64)),

@@ -429,6 +429,15 @@ std::map<std::string, typename Factory<T>::BlockFactory>& Factory<T>::block_reg(
         std::vector<int32_t> ptr(pm->jc.begin(), pm->jc.end()), ind(pm->ir.begin(), pm->ir.begin() + nnz);
         return BlockKronSparse<T>::CreateFromCSC(id_first != 0, row, col, diaglength, nrows, ncols, nnz, val, ptr, ind);
       };
+    // the coupling of the sublabel-accurate data term: cells { nx, ny, L, left, right }; a caller that also knows the size it means the
+    // block to have appends { nrows, ncols } and gets it checked.  Every argument check is BlockDatatermSublabel<T>::Create's.
+    reg["dataterm_sublabel"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
+      if (!d || d->kind != PROST_VALUE_CELL || (d->cells.size() != 5 && d->cells.size() != 7))
+        throw Exception("BlockDatatermSublabel: the data cells are { nx, ny, L, left, right } or { nx, ny, L, left, right, nrows, ncols }.");
+      const bool declared = d->cells.size() == 7;
+      return BlockDatatermSublabel<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), GetScalarFromCell(d, 3),
+                                              GetScalarFromCell(d, 4), declared ? GetScalarFromCell(d, 5) : -1.0, declared ? GetScalarFromCell(d, 6) : -1.0);
+    };
     // the dense blocks (factory.cpp:590-601, :694-716): cell 0 is a full matrix, column-major, converted to T.  A sparse cell is refused:
     // the reference would read its value array as if it were the full matrix.
     auto dense_data = [](const prost_value* pm) {

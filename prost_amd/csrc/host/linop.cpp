@@ -5,10 +5,12 @@
 #include <atomic>
 #include <cstring>
 #include <mutex>
+#include <sstream>
 #include <unordered_map>
 
 #include "hipapi.hpp"
 #include "prost/linop/blocks.hpp"
+#include "prost/linop/dataterm_sublabel.hpp"
 #include "prost/linop/linearoperator.hpp"
 
 namespace prost {
@@ -449,6 +451,75 @@ template <typename T> void BlockKronDense<T>::EvalLocal(T* r, T*, const T* x, co
 template <typename T> void BlockKronDense<T>::EvalAdjointLocal(T* r, T*, const T* x, const T*) { Product(r, x, true, false); }
 template class BlockKronDense<float>;
 template class BlockKronDense<double>;
+
+// ---- the coupling of the sublabel-accurate data term ----
+template <typename T>
+BlockDatatermSublabel<T>* BlockDatatermSublabel<T>::Create(size_t row, size_t col, double nx, double ny, double L, double left, double right,
+                                                           double declared_rows, double declared_cols) {
+  std::stringstream ss;
+  ss << "BlockDatatermSublabel: ";
+  const double kMaxCount = 9007199254740992.0;      // 2^53: counts arrive as doubles
+  if (!(L >= 2) || L != std::floor(L) || L > kMaxCount) { ss << "L = " << L << " labels, at least 2 are needed."; throw Exception(ss.str()); }
+  if (!(nx >= 1) || !(ny >= 1) || nx != std::floor(nx) || ny != std::floor(ny) || nx * ny * (L - 1) > kMaxCount / 4) {
+    ss << "nx = " << nx << " and ny = " << ny << " have to be at least 1."; throw Exception(ss.str());
+  }
+  if (!std::isfinite(left) || !std::isfinite(right)) { ss << "the bounds left = " << left << " and right = " << right << " have to be finite."; throw Exception(ss.str()); }
+  if (!(left < right)) { ss << "left = " << left << " has to be below right = " << right << "."; throw Exception(ss.str()); }
+  const double size = 2 * nx * ny * (L - 1);
+  if ((declared_rows >= 0 || declared_cols >= 0) && (declared_rows != size || declared_cols != size)) {
+    ss << "the declared size " << declared_rows << " x " << declared_cols << " is not 2 nx ny (L - 1) = " << size << " square."; throw Exception(ss.str());
+  }
+  return new BlockDatatermSublabel<T>(row, col, (size_t)nx * (size_t)ny, (size_t)L, left, right);
+}
+template <typename T>
+BlockDatatermSublabel<T>::BlockDatatermSublabel(size_t row, size_t col, size_t npixels, size_t L, double left, double right)
+    : Block<T>(row, col, 2 * npixels * (L - 1), 2 * npixels * (L - 1)), npixels_(npixels), L_(L), gamma_(L - 1) {
+  dataterm_sublabel::Labels<T>(L, left, right, delta_, gamma_.data());
+}
+template <typename T>
+void BlockDatatermSublabel<T>::Initialize() { d_gamma_ = gamma_; }
+template <typename T>
+void BlockDatatermSublabel<T>::Release() { d_gamma_.clear(); }
+template <typename T>
+T BlockDatatermSublabel<T>::row_sum(size_t row, T alpha) const {
+  const size_t k = L_ - 1, i = (row / npixels_) % k;
+  return row < npixels_ * k ? dataterm_sublabel::RowSumR<T>(i, k, delta_, gamma_[i], alpha) : dataterm_sublabel::RowSumS<T>(alpha);
+}
+template <typename T>
+T BlockDatatermSublabel<T>::col_sum(size_t col, T alpha) const {
+  const size_t k = L_ - 1, i = (col / npixels_) % k;
+  return col < npixels_ * k ? dataterm_sublabel::ColSumU<T>(delta_, alpha) : dataterm_sublabel::ColSumW<T>(i, delta_, gamma_[i], alpha);
+}
+template <typename T>
+void BlockDatatermSublabel<T>::row_sums(T* out, T alpha) const {
+  const size_t k = L_ - 1;
+  for (size_t i = 0; i < 2 * k; i++) {
+    const T v = row_sum(i * npixels_, alpha);
+    T* o = out + i * npixels_;
+    for (size_t p = 0; p < npixels_; p++) o[p] += v;
+  }
+}
+template <typename T>
+void BlockDatatermSublabel<T>::col_sums(T* out, T alpha) const {
+  const size_t k = L_ - 1;
+  for (size_t i = 0; i < 2 * k; i++) {
+    const T v = col_sum(i * npixels_, alpha);
+    T* o = out + i * npixels_;
+    for (size_t p = 0; p < npixels_; p++) o[p] += v;
+  }
+}
+template <typename T>
+void BlockDatatermSublabel<T>::Product(T* r, const T* x, bool transpose, bool acc) {
+  if (d_gamma_.size() != gamma_.size()) throw Exception("BlockDatatermSublabel used before Initialize().");
+  CheckHip(Api<T>::linop_dataterm_sublabel(r, x, npixels_, L_, d_gamma_.data(), (double)delta_, transpose ? 1 : 0, acc ? 1 : 0, CurrentStream()),
+           "linop_dataterm_sublabel");
+}
+template <typename T> void BlockDatatermSublabel<T>::EvalLocalAdd(T* r, T*, const T* x, const T*) { Product(r, x, false, true); }
+template <typename T> void BlockDatatermSublabel<T>::EvalAdjointLocalAdd(T* r, T*, const T* x, const T*) { Product(r, x, true, true); }
+template <typename T> void BlockDatatermSublabel<T>::EvalLocal(T* r, T*, const T* x, const T*) { Product(r, x, false, false); }
+template <typename T> void BlockDatatermSublabel<T>::EvalAdjointLocal(T* r, T*, const T* x, const T*) { Product(r, x, true, false); }
+template class BlockDatatermSublabel<float>;
+template class BlockDatatermSublabel<double>;
 
 // ---- diags block ----
 static bool g_diags_quirk = false;
