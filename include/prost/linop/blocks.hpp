@@ -4,6 +4,7 @@
 #define PROST_LINOP_BLOCKS_HPP_
 #include "prost/device_vector.hpp"
 #include "prost/linop/block.hpp"
+#include "prost/linop/conv2d.hpp"
 
 namespace prost {
 
@@ -235,6 +236,40 @@ class BlockDatatermSublabel : public Block<T> {
   T delta_;
   std::vector<T> gamma_;          ///< gamma_i = left + i delta, i < L - 1 (formed in double, rounded to T)
   device_vector<T> d_gamma_;
+};
+
+/// one small window applied at every pixel of L column-major image planes of ny x nx, zero padding, shape "full" / "same" / "valid",
+/// without a matrix: the blur operator of a deblurring problem (the reference's example hands kron(speye(nc), convmtx2(..)) over as
+/// a sparse matrix).  L my mx rows by L ny nx columns.  Arithmetic: prost/linop/conv2d.hpp.  No describe(): the block runs on the
+/// generic paths.  Only O(taps) data is stored: one tap table per direction.
+template <typename T>
+class BlockConv2D : public Block<T> {
+ public:
+  /// checks every argument (messages start with "BlockConv2D: "); kernel: ky x kx, column-major; declared_rows / declared_cols < 0:
+  /// no size was declared
+  static BlockConv2D<T>* Create(size_t row, size_t col, double nx, double ny, double L, const std::vector<double>& kernel, size_t ky, size_t kx,
+                                const std::string& shape, double declared_rows = -1, double declared_cols = -1);
+  virtual void Initialize();
+  virtual void Release();
+  virtual T row_sum(size_t row, T alpha) const;
+  virtual T col_sum(size_t col, T alpha) const;
+  virtual void row_sums(T* out, T alpha) const;              ///< O(rows + taps (ky + kx)): one table of rectangle sums per call
+  virtual void col_sums(T* out, T alpha) const;
+  virtual size_t gpu_mem_amount() const { return (words_[0].size() + words_[1].size()) * sizeof(int32_t); }
+  size_t taps() const { return ntaps_; }
+
+ protected:
+  BlockConv2D(size_t row, size_t col, size_t nrows, size_t ncols) : Block<T>(row, col, nrows, ncols) {}
+  virtual void EvalLocalAdd(T*, T*, const T*, const T*);
+  virtual void EvalAdjointLocalAdd(T*, T*, const T*, const T*);
+  virtual void EvalLocal(T*, T*, const T*, const T*);
+  virtual void EvalAdjointLocal(T*, T*, const T*, const T*);
+  void Product(T* r, const T* x, bool transpose, bool acc);
+  conv2d::Geometry geometry_[2];           ///< the forward [0] and the adjoint [1] direction
+  std::vector<T> window_[2];               ///< the window rounded to T, and flipped in both axes
+  std::vector<int32_t> words_[2];          ///< the tap tables (conv2d::Tap<T> records) as they are uploaded
+  size_t ntaps_ = 0;
+  device_vector<int32_t> d_taps_[2];
 };
 
 /// constant-coefficient multi-diagonal block; `identity` maps here (block_diags.hpp, identity.m:11-12)

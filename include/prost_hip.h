@@ -205,6 +205,33 @@ int prost_hip_linop_dataterm_sublabel_f32(float* res, const float* rhs, size_t n
                                           void* stream);
 int prost_hip_linop_dataterm_sublabel_f64(double* res, const double* rhs, size_t npixels, size_t L, const double* gamma, double delta, int transpose, int accumulate,
                                           void* stream);
+/* BlockConv2D (additions; ABI version unchanged; kernels_linop_conv2d.hip, arithmetic and order of operations: prost/linop/conv2d.hpp):
+ * one window applied at every pixel of `planes` image planes, zero padding.  A call is ONE direction of the operator, described by its
+ * geometry record (a HOST pointer, read before the call returns): it reads `planes` column-major source planes of sny x snx from rhs and writes `planes` destination planes of
+ * dny x dnx to res,
+ *   res(y, x) = sum over the table's taps (i, j) with 0 <= y + oy - i < sny, 0 <= x + ox - j < snx  of  k(i, j) rhs(y + oy - i, x + ox - j),
+ * 0 <= oy < ky <= 31, 0 <= ox < kx <= 31.  The adjoint of a direction is the call with the window flipped in both axes, source and
+ * destination sizes exchanged and offsets (ky - 1 - oy, kx - 1 - ox).  taps: ntaps records in device memory, one per non-zero tap, in
+ * the order they are to be added (ascending offset: j descending, inside that i descending), offset = (ky - 1 - i) +
+ * (kx - 1 - j) * PROST_HIP_CONV2D_PITCH, value already rounded to T; the table is trusted (an offset outside the window reads outside
+ * the staged tile).  accumulate != 0 stores res + value instead of value.  Any alignment of T is accepted.  Aliasing: res and rhs must
+ * NOT overlap, not even as the same pointer (a tile reads source cells that other tiles write as destinations), and the table overlaps
+ * neither.  No atomics: a call repeats its bits.  No allocation, copy or synchronisation. */
+#define PROST_HIP_CONV2D_PITCH 94
+#define PROST_HIP_CONV2D_MAX_WINDOW 31
+typedef struct prost_hip_conv2d_geometry {
+  int32_t sny, snx;     /* source plane */
+  int32_t dny, dnx;     /* destination plane */
+  int32_t oy, ox;       /* crop offset into the full convolution of the source with this direction's window */
+  int32_t ky, kx;       /* window */
+  int32_t planes;
+} prost_hip_conv2d_geometry;
+typedef struct prost_hip_conv2d_tap_f32 { int32_t offset; float value; } prost_hip_conv2d_tap_f32;
+typedef struct prost_hip_conv2d_tap_f64 { int32_t offset; int32_t reserved; double value; } prost_hip_conv2d_tap_f64;
+int prost_hip_conv2d_f32(const prost_hip_conv2d_geometry* geometry, const prost_hip_conv2d_tap_f32* taps, size_t ntaps, float* res, const float* rhs,
+                         int accumulate, void* stream);
+int prost_hip_conv2d_f64(const prost_hip_conv2d_geometry* geometry, const prost_hip_conv2d_tap_f64* taps, size_t ntaps, double* res, const double* rhs,
+                         int accumulate, void* stream);
 /* x = beta * x (beta == 0 -> zero fill): thrust::fill / transform at linearoperator.cu:140-147 */
 /* x[i] = value (thrust::fill, linearoperator.cu:140-147; also used for preconditioners that are one constant: the
  * gradient blocks' row / column sums are, block_gradient2d.cu:154-163, so nothing is uploaded for them) */

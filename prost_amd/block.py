@@ -106,6 +106,54 @@ def dataterm_sublabel(nx, ny, L, left, right):
     return lambda row, col, nrows, ncols: [["dataterm_sublabel", row, col, data], sz]
 
 
+CONV2D_MAX_WINDOW = 31
+
+
+def conv2d_size(nx, ny, ky, kx, shape):
+    """-> (my, mx), (oy, ox): the output size and the crop offset into the full convolution"""
+    if shape == "full":
+        return (ny + ky - 1, nx + kx - 1), (0, 0)
+    if shape == "same":
+        return (ny, nx), (ky // 2, kx // 2)
+    if shape == "valid":
+        return (ny - ky + 1, nx - kx + 1), (ky - 1, kx - 1)
+    raise ValueError("conv2d: unknown shape %r (full, same or valid)" % (shape,))
+
+
+def conv2d(nx, ny, L, kernel, shape="full"):
+    """2-D convolution of L column-major image planes of ny x nx (element (y, x, c) at y + x ny + c nx ny, the layout of
+    gradient2d(nx, ny, L)) with one ky x kx window, zero padding, applied without a matrix:
+    out(y, x) = sum_{i, j} kernel[i, j] in(y + oy - i, x + ox - j).  shape "full": (ny + ky - 1) x (nx + kx - 1) outputs per plane, the
+    matrix kron(eye(L), convmtx2(kernel, ny, nx)); "same": ny x nx, MATLAB's conv2(.., 'same'); "valid": (ny - ky + 1) x (nx - kx + 1).
+    Windows up to 31 x 31."""
+    for name, v in (("nx", nx), ("ny", ny), ("L", L)):
+        if isinstance(v, bool) or not np.isfinite(v) or int(v) != v:
+            raise ValueError("conv2d: %s = %r is not an integer" % (name, v))
+        if v < 1:
+            raise ValueError("conv2d: %s = %r has to be at least 1" % (name, v))
+    nx, ny, L = int(nx), int(ny), int(L)
+    kernel = np.array(kernel, dtype=np.float64, order="F", copy=True)
+    if kernel.ndim != 2 or kernel.size == 0:
+        raise ValueError("conv2d: the window has to be a non-empty matrix (2-D), got shape %r" % (kernel.shape,))
+    ky, kx = kernel.shape
+    if ky > CONV2D_MAX_WINDOW or kx > CONV2D_MAX_WINDOW:
+        raise ValueError("conv2d: the window is %d x %d, windows up to %d x %d are supported" % (ky, kx, CONV2D_MAX_WINDOW, CONV2D_MAX_WINDOW))
+    if not np.isfinite(kernel).all():
+        raise ValueError("conv2d: the window holds a non-finite value")
+    if not kernel.any():
+        raise ValueError("conv2d: the window has no non-zero tap")
+    if not isinstance(shape, str):
+        raise ValueError("conv2d: unknown shape %r (full, same or valid)" % (shape,))
+    (my, mx), _ = conv2d_size(nx, ny, ky, kx, shape)
+    if my < 1 or mx < 1:
+        raise ValueError("conv2d: the window (%d x %d) is larger than the image (%d x %d): the valid part is empty" % (ky, kx, ny, nx))
+    if nx * ny >= 2 ** 31 or my * mx >= 2 ** 31:
+        raise ValueError("conv2d: a plane of %d elements; it has to stay below 2^31" % max(nx * ny, my * mx))
+    sz = [L * my * mx, L * ny * nx]
+    data = [nx, ny, L, kernel, shape]
+    return lambda row, col, nrows, ncols: [["conv2d", row, col, data], sz]
+
+
 def diags(nrows, ncols, factors, offsets):
     sz = [nrows, ncols]
     data = [nrows, ncols, np.atleast_1d(np.asarray(factors, dtype=np.float64)),

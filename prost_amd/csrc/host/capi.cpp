@@ -438,6 +438,19 @@ std::map<std::string, typename Factory<T>::BlockFactory>& Factory<T>::block_reg(
       return BlockDatatermSublabel<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), GetScalarFromCell(d, 3),
                                               GetScalarFromCell(d, 4), declared ? GetScalarFromCell(d, 5) : -1.0, declared ? GetScalarFromCell(d, 6) : -1.0);
     };
+    // 2-D convolution without a matrix: cells { nx, ny, L, kernel (ky x kx full matrix), shape }; a caller that also knows the size it means
+    // the block to have appends { nrows, ncols } and gets it checked.  Every argument check is BlockConv2D<T>::Create's.
+    reg["conv2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
+      if (!d || d->kind != PROST_VALUE_CELL || (d->cells.size() != 5 && d->cells.size() != 7))
+        throw Exception("BlockConv2D: the data cells are { nx, ny, L, kernel, shape } or { nx, ny, L, kernel, shape, nrows, ncols }.");
+      const prost_value* pm = d->cells[3];
+      if (!pm || pm->kind != PROST_VALUE_MATRIX) throw Exception("BlockConv2D: the window has to be a full matrix of type single or double.");
+      if (!d->cells[4] || d->cells[4]->kind != PROST_VALUE_STRING) throw Exception("BlockConv2D: the shape has to be a string (full, same or valid).");
+      const bool declared = d->cells.size() == 7;
+      return BlockConv2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2),
+                                    std::vector<double>(pm->data.begin(), pm->data.begin() + pm->rows * pm->cols), pm->rows, pm->cols, d->cells[4]->str,
+                                    declared ? GetScalarFromCell(d, 5) : -1.0, declared ? GetScalarFromCell(d, 6) : -1.0);
+    };
     // the dense blocks (factory.cpp:590-601, :694-716): cell 0 is a full matrix, column-major, converted to T.  A sparse cell is refused:
     // the reference would read its value array as if it were the full matrix.
     auto dense_data = [](const prost_value* pm) {

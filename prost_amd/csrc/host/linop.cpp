@@ -10,6 +10,7 @@
 
 #include "hipapi.hpp"
 #include "prost/linop/blocks.hpp"
+#include "prost/linop/conv2d.hpp"
 #include "prost/linop/dataterm_sublabel.hpp"
 #include "prost/linop/linearoperator.hpp"
 
@@ -520,6 +521,91 @@ template <typename T> void BlockDatatermSublabel<T>::EvalLocal(T* r, T*, const T
 template <typename T> void BlockDatatermSublabel<T>::EvalAdjointLocal(T* r, T*, const T* x, const T*) { Product(r, x, true, false); }
 template class BlockDatatermSublabel<float>;
 template class BlockDatatermSublabel<double>;
+
+// ---- one window at every pixel: 2-D convolution without a matrix ----
+template <typename T>
+BlockConv2D<T>* BlockConv2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, const std::vector<double>& kernel, size_t ky, size_t kx,
+                                       const std::string& shape, double declared_rows, double declared_cols) {
+  std::stringstream ss;
+  ss << "BlockConv2D: ";
+  const double kMaxPlane = 2147483648.0;      // 2^31
+  for (const auto& v : {std::make_pair("nx", nx), std::make_pair("ny", ny), std::make_pair("L", L)})
+    if (!(v.second >= 1) || v.second != std::floor(v.second) || v.second >= kMaxPlane) {
+      ss << v.first << " = " << v.second << " has to be a positive integer below 2^31."; throw Exception(ss.str());
+    }
+  if (ky == 0 || kx == 0 || kernel.size() != ky * kx) { ss << "the window is empty."; throw Exception(ss.str()); }
+  if (ky > (size_t)conv2d::kMaxWindow || kx > (size_t)conv2d::kMaxWindow) {
+    ss << "the window is " << ky << " x " << kx << ", windows up to " << conv2d::kMaxWindow << " x " << conv2d::kMaxWindow << " are supported."; throw Exception(ss.str());
+  }
+  for (double v : kernel)
+    if (!std::isfinite(v)) { ss << "the window holds a non-finite value."; throw Exception(ss.str()); }
+  int which = -1;
+  if (shape == "full") which = conv2d::kFull;
+  else if (shape == "same") which = conv2d::kSame;
+  else if (shape == "valid") which = conv2d::kValid;
+  else { ss << "unknown shape '" << shape << "' (full, same or valid)."; throw Exception(ss.str()); }
+  long my = 0, mx = 0, oy = 0, ox = 0;
+  if (!conv2d::OutputSize(which, (long)ny, (long)nx, (long)ky, (long)kx, my, mx, oy, ox)) {
+    ss << "the window (" << ky << " x " << kx << ") is larger than the image (" << ny << " x " << nx << "): the valid part is empty."; throw Exception(ss.str());
+  }
+  if (nx * ny >= kMaxPlane || (double)my * (double)mx >= kMaxPlane) { ss << "a plane of " << std::max(nx * ny, (double)my * (double)mx) << " elements; it has to stay below 2^31."; throw Exception(ss.str()); }
+  const double rows = L * (double)my * (double)mx, cols = L * ny * nx;
+  if ((declared_rows >= 0 || declared_cols >= 0) && (declared_rows != rows || declared_cols != cols)) {
+    ss << "the declared size " << declared_rows << " x " << declared_cols << " is not L my mx x L ny nx = " << rows << " x " << cols << "."; throw Exception(ss.str());
+  }
+  std::unique_ptr<BlockConv2D<T>> b(new BlockConv2D<T>(row, col, (size_t)rows, (size_t)cols));
+  for (int dir = 0; dir < 2; dir++) {
+    b->geometry_[dir] = conv2d::MakeGeometry(which, (long)ny, (long)nx, (long)ky, (long)kx, (long)L, dir == 1);
+    b->window_[dir] = conv2d::Window<T>(kernel.data(), (long)ky, (long)kx, dir == 1);
+    const std::vector<conv2d::Tap<T>> taps = conv2d::CompactTaps<T>(b->window_[dir], (long)ky, (long)kx);
+    static_assert(sizeof(conv2d::Tap<T>) % sizeof(int32_t) == 0, "tap record in words");
+    b->words_[dir].assign(taps.size() * (sizeof(conv2d::Tap<T>) / sizeof(int32_t)), 0);
+    for (size_t t = 0; t < taps.size(); t++) {     // field by field: the padding of the fp64 record stays zero
+      int32_t* w = b->words_[dir].data() + t * (sizeof(conv2d::Tap<T>) / sizeof(int32_t));
+      std::memcpy(w, &taps[t].offset, sizeof(int32_t));
+      std::memcpy(reinterpret_cast<char*>(w) + offsetof(conv2d::Tap<T>, value), &taps[t].value, sizeof(T));
+    }
+    b->ntaps_ = taps.size();
+  }
+  if (b->ntaps_ == 0) { ss << "the window has no non-zero tap" << (std::is_same<T, float>::value ? " in single precision." : "."); throw Exception(ss.str()); }
+  return b.release();
+}
+template <typename T>
+void BlockConv2D<T>::Initialize() { for (int dir = 0; dir < 2; dir++) d_taps_[dir] = words_[dir]; }
+template <typename T>
+void BlockConv2D<T>::Release() { for (int dir = 0; dir < 2; dir++) d_taps_[dir].clear(); }
+template <typename T>
+T BlockConv2D<T>::row_sum(size_t row, T alpha) const {
+  const conv2d::Geometry& g = geometry_[0];
+  const size_t p = row % ((size_t)g.dny * (size_t)g.dnx);
+  return (T)conv2d::SumAt<T>(g, window_[0], (double)alpha, (int)(p % (size_t)g.dny), (int)(p / (size_t)g.dny));
+}
+template <typename T>
+T BlockConv2D<T>::col_sum(size_t col, T alpha) const {
+  const conv2d::Geometry& g = geometry_[1];
+  const size_t p = col % ((size_t)g.dny * (size_t)g.dnx);
+  return (T)conv2d::SumAt<T>(g, window_[1], (double)alpha, (int)(p % (size_t)g.dny), (int)(p / (size_t)g.dny));
+}
+template <typename T>
+void BlockConv2D<T>::row_sums(T* out, T alpha) const { conv2d::RowSums<T>(geometry_[0], window_[0], (double)alpha, out); }
+template <typename T>
+void BlockConv2D<T>::col_sums(T* out, T alpha) const { conv2d::RowSums<T>(geometry_[1], window_[1], (double)alpha, out); }
+template <typename T>
+void BlockConv2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
+  const int dir = transpose ? 1 : 0;
+  if (d_taps_[dir].size() != words_[dir].size()) throw Exception("BlockConv2D used before Initialize().");
+  typedef typename std::conditional<std::is_same<T, float>::value, prost_hip_conv2d_tap_f32, prost_hip_conv2d_tap_f64>::type Record;
+  static_assert(sizeof(Record) == sizeof(conv2d::Tap<T>) && sizeof(prost_hip_conv2d_geometry) == sizeof(conv2d::Geometry), "records of prost_hip.h");
+  CheckHip(Api<T>::conv2d(reinterpret_cast<const prost_hip_conv2d_geometry*>(&geometry_[dir]), reinterpret_cast<const Record*>(d_taps_[dir].data()), ntaps_, r, x,
+                          acc ? 1 : 0, CurrentStream()),
+           "conv2d");
+}
+template <typename T> void BlockConv2D<T>::EvalLocalAdd(T* r, T*, const T* x, const T*) { Product(r, x, false, true); }
+template <typename T> void BlockConv2D<T>::EvalAdjointLocalAdd(T* r, T*, const T* x, const T*) { Product(r, x, true, true); }
+template <typename T> void BlockConv2D<T>::EvalLocal(T* r, T*, const T* x, const T*) { Product(r, x, false, false); }
+template <typename T> void BlockConv2D<T>::EvalAdjointLocal(T* r, T*, const T* x, const T*) { Product(r, x, true, false); }
+template class BlockConv2D<float>;
+template class BlockConv2D<double>;
 
 // ---- diags block ----
 static bool g_diags_quirk = false;
