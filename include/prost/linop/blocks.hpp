@@ -5,6 +5,7 @@
 #include "prost/device_vector.hpp"
 #include "prost/linop/block.hpp"
 #include "prost/linop/conv2d.hpp"
+#include "prost/linop/sym_gradient2d.hpp"
 
 namespace prost {
 
@@ -270,6 +271,36 @@ class BlockConv2D : public Block<T> {
   std::vector<int32_t> words_[2];          ///< the tap tables (conv2d::Tap<T> records) as they are uploaded
   size_t ntaps_ = 0;
   device_vector<int32_t> d_taps_[2];
+};
+
+/// the symmetrised gradient of a vector field on L channels of an ny x nx grid, without a matrix: the second-order operator of TGV^2
+/// (K = [grad -I ; 0 E]).  3 L N rows (exx, eyy, exy planes) by 2 L N columns (vx, vy planes, the range layout of gradient2d), backward
+/// differences with the boundary handling of the divergence, the mixed rows weighted by w.  Arithmetic: prost/linop/sym_gradient2d.hpp.
+/// No describe(): the block runs on the generic paths.  Nothing is stored on the device.
+template <typename T>
+class BlockSymGradient2D : public Block<T> {
+ public:
+  /// checks every argument (messages start with "BlockSymGradient2D: "); declared_rows / declared_cols < 0: no size was declared
+  static BlockSymGradient2D<T>* Create(size_t row, size_t col, double nx, double ny, double L, double w, double declared_rows = -1, double declared_cols = -1);
+  virtual void Initialize() {}
+  virtual void Release() {}
+  virtual T row_sum(size_t row, T alpha) const;
+  virtual T col_sum(size_t col, T alpha) const;
+  virtual void row_sums(T* out, T alpha) const;              ///< closed forms, one pass over the rows
+  virtual void col_sums(T* out, T alpha) const;
+  virtual size_t gpu_mem_amount() const { return 0; }
+
+ protected:
+  BlockSymGradient2D(size_t row, size_t col, size_t nx, size_t ny, size_t L, double w)
+      : Block<T>(row, col, 3 * L * nx * ny, 2 * L * nx * ny), nx_(nx), ny_(ny), L_(L), w_(w) {}
+  virtual void EvalLocalAdd(T*, T*, const T*, const T*);
+  virtual void EvalAdjointLocalAdd(T*, T*, const T*, const T*);
+  virtual void EvalLocal(T*, T*, const T*, const T*);
+  virtual void EvalAdjointLocal(T*, T*, const T*, const T*);
+  void Product(T* r, const T* x, bool transpose, bool acc);
+  double WeightPower(T alpha) const { return sym_gradient2d::WeightPower((double)sym_gradient2d::RoundWeight<T>(w_), (double)alpha); }
+  size_t nx_, ny_, L_;
+  double w_;               ///< as given; the kernels and the sums round it to T once
 };
 
 /// constant-coefficient multi-diagonal block; `identity` maps here (block_diags.hpp, identity.m:11-12)

@@ -232,6 +232,22 @@ int prost_hip_conv2d_f32(const prost_hip_conv2d_geometry* geometry, const prost_
                          int accumulate, void* stream);
 int prost_hip_conv2d_f64(const prost_hip_conv2d_geometry* geometry, const prost_hip_conv2d_tap_f64* taps, size_t ntaps, double* res, const double* rhs,
                          int accumulate, void* stream);
+/* BlockSymGradient2D (additions; ABI version unchanged; kernels_linop_sym_gradient2d.hip, arithmetic and order of operations:
+ * prost/linop/sym_gradient2d.hpp): the symmetrised gradient E of a vector field on L channels of an ny x nx grid, N = nx ny, pixel
+ * (y, x) at p = y + x ny.  Domain, 2 L N values: vx_c[p] at c N + p, vy_c[p] at (L + c) N + p (the range layout of gradient2d).  Range,
+ * 3 L N values: exx_c[p] at c N + p, eyy_c[p] at (L + c) N + p, exy_c[p] at (2 L + c) N + p.  With ax = [x < nx-1], bx = [x > 0],
+ * ay = [y < ny-1], by = [y > 0], a sum starts from +0 and adds its present terms left to right (ascending column index of the explicit
+ * matrix); a masked term is absent, not multiplied by zero; w is rounded to T once and every product w a is rounded on its own:
+ *   transpose == 0:  exx[p] = (bx) -vx[p-ny], (ax) +vx[p];   eyy[p] = (by) -vy[p-1], (ay) +vy[p];
+ *                    exy[p] = (by) -(w vx[p-1]), (ay) +(w vx[p]), (bx) -(w vy[p-ny]), (ax) +(w vy[p])
+ *   transpose != 0:  vx[p] = (ax) +exx[p], (ax) -exx[p+ny], (ay) +(w exy[p]), (ay) -(w exy[p+1]);
+ *                    vy[p] = (ay) +eyy[p], (ay) -eyy[p+1], (ax) +(w exy[p]), (ax) -(w exy[p+ny])
+ * accumulate != 0 stores res + value instead of value.  Any alignment of T is accepted (16-byte aligned pointers and a height that
+ * is a multiple of 16 / sizeof(T) take the vector kernels; the bits are the same).  Aliasing: res and rhs must NOT overlap, not even as
+ * the same pointer.  No atomics: a call repeats its bits.  No allocation, copy or synchronisation.  Refused without a launch: nx, ny
+ * or L of 0, w not finite, w zero after rounding to T, null pointers, 3 L N beyond 2^53. */
+int prost_hip_linop_sym_gradient2d_f32(float* res, const float* rhs, size_t nx, size_t ny, size_t L, double w, int transpose, int accumulate, void* stream);
+int prost_hip_linop_sym_gradient2d_f64(double* res, const double* rhs, size_t nx, size_t ny, size_t L, double w, int transpose, int accumulate, void* stream);
 /* x = beta * x (beta == 0 -> zero fill): thrust::fill / transform at linearoperator.cu:140-147 */
 /* x[i] = value (thrust::fill, linearoperator.cu:140-147; also used for preconditioners that are one constant: the
  * gradient blocks' row / column sums are, block_gradient2d.cu:154-163, so nothing is uploaded for them) */

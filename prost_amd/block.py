@@ -4,6 +4,8 @@ Each builder returns ``func(row, col, nrows, ncols) -> [[name, row, col, data], 
 exactly like the MATLAB closures (gradient2d.m:12-14, gradient3d.m:12-14, sparse.m:6-9,
 diags.m:17-20, identity.m:11-12, zero.m:3-4, dense.m, dense_kron_id.m, id_kron_dense.m).  Cells are Python lists.
 """
+import math
+
 import numpy as np
 
 
@@ -152,6 +154,35 @@ def conv2d(nx, ny, L, kernel, shape="full"):
     sz = [L * my * mx, L * ny * nx]
     data = [nx, ny, L, kernel, shape]
     return lambda row, col, nrows, ncols: [["conv2d", row, col, data], sz]
+
+
+SYM_GRADIENT2D_MAX_SIZE = 2 ** 53          # sizes travel as doubles
+
+
+def sym_gradient2d(nx, ny, L=1, w=math.sqrt(0.5)):
+    """The symmetrised gradient E of a vector field on L channels of an ny x nx grid, applied without a matrix: the second-order
+    operator of total generalised variation, K = [grad -I ; 0 E].  N = nx ny, pixel (y, x) at p = y + x ny.  Domain, 2 L N values, the
+    range layout of gradient2d(nx, ny, L): vx_c[p] at c N + p, vy_c[p] at (L + c) N + p.  Range, 3 L N values: exx_c[p] at c N + p,
+    eyy_c[p] at (L + c) N + p, exy_c[p] at (2 L + c) N + p, so sum_norm2(3, False, ..) groups per channel and pixel.  Backward
+    differences with the boundary handling of the divergence (Bx = -Dx^T, By = -Dy^T of gradient2d's forward differences):
+    exx = Bx vx, eyy = By vy, exy = w (By vx + Bx vy).  w = sqrt(1/2): the 2-norm of (exx, eyy, exy) is the Frobenius norm of the
+    symmetrised Jacobian; w = 0.5: the entries of (J + J^T) / 2."""
+    for name, v in (("nx", nx), ("ny", ny), ("L", L)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or int(v) != v:
+            raise ValueError("sym_gradient2d: %s = %r is not an integer" % (name, v))
+        if v < 1:
+            raise ValueError("sym_gradient2d: %s = %r has to be at least 1" % (name, v))
+    nx, ny, L = int(nx), int(ny), int(L)
+    if isinstance(w, bool) or not isinstance(w, (int, float, np.integer, np.floating)) or not np.isfinite(w):
+        raise ValueError("sym_gradient2d: w = %r is not a finite number" % (w,))
+    w = float(w)
+    if w == 0:
+        raise ValueError("sym_gradient2d: w has to be non-zero")
+    if 3 * L * nx * ny > SYM_GRADIENT2D_MAX_SIZE:
+        raise ValueError("sym_gradient2d: 3 L nx ny = %d rows; the size has to stay within 2^53" % (3 * L * nx * ny))
+    sz = [3 * L * nx * ny, 2 * L * nx * ny]
+    data = [nx, ny, L, w]
+    return lambda row, col, nrows, ncols: [["sym_gradient2d", row, col, data], sz]
 
 
 def diags(nrows, ncols, factors, offsets):

@@ -451,6 +451,15 @@ std::map<std::string, typename Factory<T>::BlockFactory>& Factory<T>::block_reg(
                                     std::vector<double>(pm->data.begin(), pm->data.begin() + pm->rows * pm->cols), pm->rows, pm->cols, d->cells[4]->str,
                                     declared ? GetScalarFromCell(d, 5) : -1.0, declared ? GetScalarFromCell(d, 6) : -1.0);
     };
+    // the symmetrised gradient of TGV^2 without a matrix: cells { nx, ny, L, w }; a caller that also knows the size it means the block to
+    // have appends { nrows, ncols } and gets it checked.  Every argument check is BlockSymGradient2D<T>::Create's.
+    reg["sym_gradient2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
+      if (!d || d->kind != PROST_VALUE_CELL || (d->cells.size() != 4 && d->cells.size() != 6))
+        throw Exception("BlockSymGradient2D: the data cells are { nx, ny, L, w } or { nx, ny, L, w, nrows, ncols }.");
+      const bool declared = d->cells.size() == 6;
+      return BlockSymGradient2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), GetScalarFromCell(d, 3),
+                                           declared ? GetScalarFromCell(d, 4) : -1.0, declared ? GetScalarFromCell(d, 5) : -1.0);
+    };
     // the dense blocks (factory.cpp:590-601, :694-716): cell 0 is a full matrix, column-major, converted to T.  A sparse cell is refused:
     // the reference would read its value array as if it were the full matrix.
     auto dense_data = [](const prost_value* pm) {

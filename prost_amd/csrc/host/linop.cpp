@@ -607,6 +607,52 @@ template <typename T> void BlockConv2D<T>::EvalAdjointLocal(T* r, T*, const T* x
 template class BlockConv2D<float>;
 template class BlockConv2D<double>;
 
+// ---- the symmetrised gradient of TGV^2, without a matrix ----
+template <typename T>
+BlockSymGradient2D<T>* BlockSymGradient2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, double w, double declared_rows, double declared_cols) {
+  std::stringstream ss;
+  ss << "BlockSymGradient2D: ";
+  const double kMaxSize = 9007199254740992.0;      // 2^53: sizes travel as doubles
+  for (const auto& v : {std::make_pair("nx", nx), std::make_pair("ny", ny), std::make_pair("L", L)})
+    if (!(v.second >= 1) || v.second != std::floor(v.second) || v.second > kMaxSize) {
+      ss << v.first << " = " << v.second << " has to be a positive integer."; throw Exception(ss.str());
+    }
+  if (!std::isfinite(w)) { ss << "w = " << w << " has to be finite."; throw Exception(ss.str()); }
+  if (w == 0) { ss << "w has to be non-zero."; throw Exception(ss.str()); }
+  const T wt = sym_gradient2d::RoundWeight<T>(w);
+  if (wt == (T)0 || !std::isfinite((double)wt)) {
+    ss << "w = " << w << " is zero or not finite" << (std::is_same<T, float>::value ? " in single precision." : "."); throw Exception(ss.str());
+  }
+  const double rows = 3 * L * nx * ny, cols = 2 * L * nx * ny;
+  if (!(3 * L * (nx * ny) <= kMaxSize) || !(nx * ny <= kMaxSize)) { ss << "3 L nx ny = " << rows << " rows; the size has to stay within 2^53."; throw Exception(ss.str()); }
+  if ((declared_rows >= 0 || declared_cols >= 0) && (declared_rows != rows || declared_cols != cols)) {
+    ss << "the declared size " << declared_rows << " x " << declared_cols << " is not 3 L nx ny x 2 L nx ny = " << rows << " x " << cols << "."; throw Exception(ss.str());
+  }
+  return new BlockSymGradient2D<T>(row, col, (size_t)nx, (size_t)ny, (size_t)L, w);
+}
+template <typename T>
+T BlockSymGradient2D<T>::row_sum(size_t row, T alpha) const { return (T)sym_gradient2d::RowSum(row, nx_, ny_, L_, WeightPower(alpha)); }
+template <typename T>
+T BlockSymGradient2D<T>::col_sum(size_t col, T alpha) const { return (T)sym_gradient2d::ColSum(col, nx_, ny_, L_, WeightPower(alpha)); }
+template <typename T>
+void BlockSymGradient2D<T>::row_sums(T* out, T alpha) const {
+  sym_gradient2d::RowSums<T>(out, nx_, ny_, L_, WeightPower(alpha));
+}
+template <typename T>
+void BlockSymGradient2D<T>::col_sums(T* out, T alpha) const {
+  sym_gradient2d::ColSums<T>(out, nx_, ny_, L_, WeightPower(alpha));
+}
+template <typename T>
+void BlockSymGradient2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
+  CheckHip(Api<T>::linop_sym_gradient2d(r, x, nx_, ny_, L_, w_, transpose ? 1 : 0, acc ? 1 : 0, CurrentStream()), "linop_sym_gradient2d");
+}
+template <typename T> void BlockSymGradient2D<T>::EvalLocalAdd(T* r, T*, const T* x, const T*) { Product(r, x, false, true); }
+template <typename T> void BlockSymGradient2D<T>::EvalAdjointLocalAdd(T* r, T*, const T* x, const T*) { Product(r, x, true, true); }
+template <typename T> void BlockSymGradient2D<T>::EvalLocal(T* r, T*, const T* x, const T*) { Product(r, x, false, false); }
+template <typename T> void BlockSymGradient2D<T>::EvalAdjointLocal(T* r, T*, const T* x, const T*) { Product(r, x, true, false); }
+template class BlockSymGradient2D<float>;
+template class BlockSymGradient2D<double>;
+
 // ---- diags block ----
 static bool g_diags_quirk = false;
 template <typename T> void BlockDiags<T>::SetReferenceGridQuirk(bool on) { g_diags_quirk = on; }
