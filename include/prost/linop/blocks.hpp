@@ -9,55 +9,63 @@
 
 namespace prost {
 
-/// forward differences with Neumann boundary, L channels (block_gradient2d.hpp / .cu:141-204)
+/// A block whose kernels take the direction and an accumulate flag: it implements ONE product, and the four evaluation entries of the
+/// plugin contract (prost::Block<T>, block.hpp -- unchanged, plugins keep deriving from it) are written here once.
 template <typename T>
-class BlockGradient2D : public Block<T> {
+class ProductBlock : public Block<T> {
  public:
-  BlockGradient2D(size_t row, size_t col, size_t nx, size_t ny, size_t L, bool label_first = false)
-      : Block<T>(row, col, nx * ny * L * 2, nx * ny * L), nx_(nx), ny_(ny), L_(L), label_first_(label_first) {}
-  virtual T row_sum(size_t, T) const { return 2; }     // block_gradient2d.cu:154-157
-  virtual T col_sum(size_t, T) const { return 4; }     // :160-163
-  virtual bool uniform_sums(T, T, T& row, T& col) const { row = 2; col = 4; return true; }
+  using Block<T>::Block;
+
+ protected:
+  /// res = K rhs, or K^T rhs (transpose); accumulate: res += ...
+  virtual void Product(T* res, const T* rhs, bool transpose, bool accumulate) = 0;
+  void EvalLocalAdd(T* res, T*, const T* rhs, const T*) final { Product(res, rhs, false, true); }
+  void EvalAdjointLocalAdd(T* res, T*, const T* rhs, const T*) final { Product(res, rhs, true, true); }
+  void EvalLocal(T* res, T*, const T* rhs, const T*) final { Product(res, rhs, false, false); }
+  void EvalAdjointLocal(T* res, T*, const T* rhs, const T*) final { Product(res, rhs, true, false); }
+};
+
+/// D = 2: forward differences with Neumann boundary, L channels (block_gradient2d.hpp / .cu:141-204); D = 3: as 2-D plus the label/z
+/// difference with Dirichlet boundary at l = L-1 (block_gradient3d.cu:73-76).  Every row sums to 2 and every column to 2 D
+/// (block_gradient2d.cu:154-163, block_gradient3d.cu:165-174).
+template <typename T, int D>
+class BlockGradient : public ProductBlock<T> {
+ public:
+  BlockGradient(size_t row, size_t col, size_t nx, size_t ny, size_t L, bool label_first = false)
+      : ProductBlock<T>(row, col, nx * ny * L * D, nx * ny * L), nx_(nx), ny_(ny), L_(L), label_first_(label_first) {}
+  virtual T row_sum(size_t, T) const { return 2; }
+  virtual T col_sum(size_t, T) const { return 2 * D; }
+  virtual bool uniform_sums(T, T, T& row, T& col) const { row = 2; col = 2 * D; return true; }
   virtual void row_sums(T* out, T alpha) const;
   virtual void col_sums(T* out, T alpha) const;
   virtual size_t gpu_mem_amount() const { return 0; }
-  virtual bool describe(BlockDesc& d) const { d.kind = BlockDesc::kGradient2D; d.nx = nx_; d.ny = ny_; d.L = L_; d.label_first = label_first_; return true; }
+  virtual bool describe(BlockDesc& d) const { d.kind = D == 2 ? BlockDesc::kGradient2D : BlockDesc::kGradient3D; d.nx = nx_; d.ny = ny_; d.L = L_; d.label_first = label_first_; return true; }
 
  protected:
-  virtual void EvalLocalAdd(T*, T*, const T*, const T*);
-  virtual void EvalAdjointLocalAdd(T*, T*, const T*, const T*);
-  virtual void EvalLocal(T*, T*, const T*, const T*);
-  virtual void EvalAdjointLocal(T*, T*, const T*, const T*);
+  virtual void Product(T* res, const T* rhs, bool transpose, bool accumulate);
   size_t nx_, ny_, L_;
   bool label_first_;
 };
+template <typename T> using BlockGradient2D = BlockGradient<T, 2>;
+template <typename T> using BlockGradient3D = BlockGradient<T, 3>;
 
-/// as 2-D plus the label/z difference with Dirichlet boundary at l = L-1 (block_gradient3d.cu:73-76)
-template <typename T>
-class BlockGradient3D : public Block<T> {
- public:
-  BlockGradient3D(size_t row, size_t col, size_t nx, size_t ny, size_t L, bool label_first = false)
-      : Block<T>(row, col, nx * ny * L * 3, nx * ny * L), nx_(nx), ny_(ny), L_(L), label_first_(label_first) {}
-  virtual T row_sum(size_t, T) const { return 2; }     // block_gradient3d.cu:165-168
-  virtual T col_sum(size_t, T) const { return 6; }     // :171-174
-  virtual bool uniform_sums(T, T, T& row, T& col) const { row = 2; col = 6; return true; }
-  virtual void row_sums(T* out, T alpha) const;
-  virtual void col_sums(T* out, T alpha) const;
-  virtual size_t gpu_mem_amount() const { return 0; }
-  virtual bool describe(BlockDesc& d) const { d.kind = BlockDesc::kGradient3D; d.nx = nx_; d.ny = ny_; d.L = L_; d.label_first = label_first_; return true; }
-
- protected:
-  virtual void EvalLocalAdd(T*, T*, const T*, const T*);
-  virtual void EvalAdjointLocalAdd(T*, T*, const T*, const T*);
-  virtual void EvalLocal(T*, T*, const T*, const T*);
-  virtual void EvalAdjointLocal(T*, T*, const T*, const T*);
-  size_t nx_, ny_, L_;
-  bool label_first_;
+/// K (side 0 of a block) or K^T (side 1) as a CSR matrix of `rows` rows with values of type V, on the host and -- between Upload() and
+/// Clear() -- on the device
+template <typename V>
+struct CsrSide {
+  size_t rows = 0;
+  std::vector<int32_t> host_ind, host_ptr;
+  std::vector<V> host_val;
+  device_vector<int32_t> ind, ptr;
+  device_vector<V> val;
+  void Upload() { ind = host_ind; ptr = host_ptr; val = host_val; }
+  void Clear() { ind.clear(); ptr.clear(); val.clear(); }
+  template <typename T> T AbsPowSum(size_t row, T alpha) const;      ///< sum_j |K_row,j|^alpha
 };
 
 /// general sparse block; K as CSR and K^T as CSR (= the CSC arrays handed in) (block_sparse.hpp)
 template <typename T>
-class BlockSparse : public Block<T> {
+class BlockSparse : public ProductBlock<T> {
  public:
   /// arrays in MATLAB CSC form: ptr = Jc (ncols+1), ind = Ir (nnz) (block_sparse.cu:34-68)
   static BlockSparse<T>* CreateFromCSC(size_t row, size_t col, int m, int n, int nnz, const std::vector<T>& val,
@@ -77,9 +85,9 @@ class BlockSparse : public Block<T> {
   static void SetPatternCompression(bool on);
   static bool pattern_compression();
   /// which of K / K^T are applied from row patterns (after Initialize()), and how many patterns each has
-  bool patterns_forward() const { return pat_.on; }
-  bool patterns_adjoint() const { return pat_t_.on; }
-  size_t pattern_count(bool adjoint) const { return (adjoint ? pat_t_ : pat_).count; }
+  bool patterns_forward() const { return side_[0].pat.on; }
+  bool patterns_adjoint() const { return side_[1].pat.on; }
+  size_t pattern_count(bool adjoint) const { return side_[adjoint].pat.count; }
   /// the matrix IS spmat_gradient2d(nx, ny, L) (matlab/+prost/+test/private/spmat_gradient2d.m:7-14), entry for entry (Initialize())
   virtual bool stencil_shape(BlockDesc& d) const {
     if (!grad_nx_) return false;
@@ -87,34 +95,16 @@ class BlockSparse : public Block<T> {
     return true;
   }
   static void SetStencilRecognition(bool on);
-  virtual bool describe(BlockDesc& d) const {
-    if (nnz_ == 0) return false;
-    if (!pat_.on && val_.size() != nnz_) return false;          // before Initialize()
-    if (!pat_t_.on && val_t_.size() != nnz_) return false;
-    d.kind = BlockDesc::kSparse; d.nnz = nnz_;
-    if (pat_.on) { d.ids = pat_.ids.data(); d.pptr = pat_.pptr.data(); d.rel = pat_.rel.data(); d.pval = pat_.val.data(); d.anchor = pat_.anchor.size() ? pat_.anchor.data() : nullptr; }
-    else { d.val = val_.data(); d.ptr = ptr_.data(); d.ind = ind_.data(); }
-    if (pat_t_.on) { d.ids_t = pat_t_.ids.data(); d.pptr_t = pat_t_.pptr.data(); d.rel_t = pat_t_.rel.data(); d.pval_t = pat_t_.val.data(); d.anchor_t = pat_t_.anchor.size() ? pat_t_.anchor.data() : nullptr; }
-    else { d.val_t = val_t_.data(); d.ptr_t = ptr_t_.data(); d.ind_t = ind_t_.data(); }
-    d.pointwise_planes = pointwise_planes_;
-    return true;
-  }
+  virtual bool describe(BlockDesc& d) const;
 
  protected:
-  BlockSparse(size_t row, size_t col, size_t nrows, size_t ncols) : Block<T>(row, col, nrows, ncols), nnz_(0) {}
-  virtual void EvalLocalAdd(T*, T*, const T*, const T*);
-  virtual void EvalAdjointLocalAdd(T*, T*, const T*, const T*);
-  virtual void EvalLocal(T*, T*, const T*, const T*);            ///< non-accumulating product in one pass (no separate zero fill)
-  virtual void EvalAdjointLocal(T*, T*, const T*, const T*);
+  BlockSparse(size_t row, size_t col, size_t nrows, size_t ncols) : ProductBlock<T>(row, col, nrows, ncols), nnz_(0) {}
+  virtual void Product(T* res, const T* rhs, bool transpose, bool accumulate);      ///< one pass either way (no separate zero fill)
   size_t nnz_;
   size_t grad_nx_ = 0, grad_ny_ = 0, grad_L_ = 0;      ///< non-zero: K == spmat_gradient2d(grad_nx_, grad_ny_, grad_L_)
   void DetectGradient2D();
   size_t pointwise_planes_ = 0;                        ///< non-zero: row i has its entries at columns i + c nrows, c < pointwise_planes_ (Initialize())
   void DetectPointwise();
-  std::vector<int32_t> host_ind_, host_ind_t_, host_ptr_, host_ptr_t_;
-  std::vector<T> host_val_, host_val_t_;
-  device_vector<int32_t> ind_, ind_t_, ptr_, ptr_t_;
-  device_vector<T> val_, val_t_;
   struct RowPatterns {
     bool on = false;
     size_t count = 0;
@@ -123,14 +113,16 @@ class BlockSparse : public Block<T> {
     device_vector<T> val;                     ///< ... and value
     device_vector<int32_t> anchor;            ///< anchored table (matrices between different geometries): offsets count from anchor[row]; empty: from the row number
   };
-  RowPatterns pat_, pat_t_;
-  void PatternProduct(const RowPatterns& p, T* r, const T* x, size_t rows, int acc);
+  /// a side that runs from row patterns keeps its CSR arrays on the host
+  struct Side : CsrSide<T> { RowPatterns pat; };
+  Side side_[2];                              ///< K and K^T
+  void PatternProduct(const Side& s, T* r, const T* x, int acc);
 };
 
 /// kron(K, I_d) (id_first == false, block_sparse_kron_id.cu) or kron(I_d, K) (id_first == true,
 /// block_id_kron_sparse.cu) for a small sparse K, without forming the product; values kept as float
 template <typename T>
-class BlockKronSparse : public Block<T> {
+class BlockKronSparse : public ProductBlock<T> {
  public:
   static BlockKronSparse<T>* CreateFromCSC(bool id_first, size_t row, size_t col, size_t diaglength, int m, int n, int nnz,
                                            const std::vector<T>& val, const std::vector<int32_t>& ptr, const std::vector<int32_t>& ind);
@@ -141,23 +133,17 @@ class BlockKronSparse : public Block<T> {
   virtual size_t gpu_mem_amount() const;
 
  protected:
-  BlockKronSparse(size_t row, size_t col, size_t nrows, size_t ncols) : Block<T>(row, col, nrows, ncols) {}
-  virtual void EvalLocalAdd(T*, T*, const T*, const T*);
-  virtual void EvalAdjointLocalAdd(T*, T*, const T*, const T*);
-  virtual void EvalLocal(T*, T*, const T*, const T*);              ///< non-accumulating forms: no fill pass in front of the product
-  virtual void EvalAdjointLocal(T*, T*, const T*, const T*);
+  BlockKronSparse(size_t row, size_t col, size_t nrows, size_t ncols) : ProductBlock<T>(row, col, nrows, ncols) {}
+  virtual void Product(T* res, const T* rhs, bool transpose, bool accumulate);      ///< no fill pass in front of the product
   bool id_first_ = false;
-  size_t diaglength_ = 0, mat_nnz_ = 0, mat_nrows_ = 0, mat_ncols_ = 0;
-  std::vector<int32_t> host_ind_, host_ind_t_, host_ptr_, host_ptr_t_;
-  std::vector<float> host_val_, host_val_t_;
-  device_vector<int32_t> ind_, ind_t_, ptr_, ptr_t_;
-  device_vector<float> val_, val_t_;
+  size_t diaglength_ = 0, mat_nnz_ = 0;
+  CsrSide<float> side_[2];      ///< K (mat_nrows rows) and K^T (mat_ncols rows); each side's column count is the other's row count
 };
 
 /// general dense block, K column-major of type T (block_dense.hpp); the products are hand-written kernels instead of gemv calls and
 /// repeat their result bit for bit from call to call
 template <typename T>
-class BlockDense : public Block<T> {
+class BlockDense : public ProductBlock<T> {
  public:
   static BlockDense<T>* CreateFromColFirstData(size_t row, size_t col, size_t nrows, size_t ncols, const std::vector<T>& data);
   virtual void Initialize();
@@ -167,12 +153,8 @@ class BlockDense : public Block<T> {
   virtual size_t gpu_mem_amount() const;
 
  protected:
-  BlockDense(size_t row, size_t col, size_t nrows, size_t ncols) : Block<T>(row, col, nrows, ncols) {}
-  virtual void EvalLocalAdd(T*, T*, const T*, const T*);
-  virtual void EvalAdjointLocalAdd(T*, T*, const T*, const T*);
-  virtual void EvalLocal(T*, T*, const T*, const T*);
-  virtual void EvalAdjointLocal(T*, T*, const T*, const T*);
-  void Product(T* r, const T* x, bool transpose, bool acc);
+  BlockDense(size_t row, size_t col, size_t nrows, size_t ncols) : ProductBlock<T>(row, col, nrows, ncols) {}
+  virtual void Product(T* res, const T* rhs, bool transpose, bool accumulate);
   std::vector<T> host_data_;
   device_vector<T> data_;
   device_vector<double> workspace_;      ///< partial sums of a split product (prost_hip_dense_gemv_workspace_bytes)
@@ -181,7 +163,7 @@ class BlockDense : public Block<T> {
 /// kron(K, I_d) (id_first == false, block_dense_kron_id.cu) or kron(I_d, K) (id_first == true, block_id_kron_dense.cu) for a small
 /// dense K, column-major, values of type T (the sparse Kronecker blocks keep float), without forming the product
 template <typename T>
-class BlockKronDense : public Block<T> {
+class BlockKronDense : public ProductBlock<T> {
  public:
   static BlockKronDense<T>* CreateFromColFirstData(bool id_first, size_t diaglength, size_t row, size_t col, size_t nrows, size_t ncols,
                                                    const std::vector<T>& data);
@@ -192,12 +174,8 @@ class BlockKronDense : public Block<T> {
   virtual size_t gpu_mem_amount() const;
 
  protected:
-  BlockKronDense(size_t row, size_t col, size_t nrows, size_t ncols) : Block<T>(row, col, nrows, ncols) {}
-  virtual void EvalLocalAdd(T*, T*, const T*, const T*);
-  virtual void EvalAdjointLocalAdd(T*, T*, const T*, const T*);
-  virtual void EvalLocal(T*, T*, const T*, const T*);
-  virtual void EvalAdjointLocal(T*, T*, const T*, const T*);
-  void Product(T* r, const T* x, bool transpose, bool acc);
+  BlockKronDense(size_t row, size_t col, size_t nrows, size_t ncols) : ProductBlock<T>(row, col, nrows, ncols) {}
+  virtual void Product(T* res, const T* rhs, bool transpose, bool accumulate);
   bool id_first_ = false;
   size_t diaglength_ = 0, mat_nrows_ = 0, mat_ncols_ = 0;
   std::vector<T> host_data_;
@@ -209,7 +187,7 @@ class BlockKronDense : public Block<T> {
 /// [u ; w] and range [r ; s] of 2 N k values each in planes of N (element (p, i) at i N + p), applied without a matrix.  Arithmetic:
 /// prost/linop/dataterm_sublabel.hpp.  No describe(): the block runs on the generic paths.
 template <typename T>
-class BlockDatatermSublabel : public Block<T> {
+class BlockDatatermSublabel : public ProductBlock<T> {
  public:
   /// checks every argument (messages start with "BlockDatatermSublabel: "); declared_rows / declared_cols < 0: no size was declared
   static BlockDatatermSublabel<T>* Create(size_t row, size_t col, double nx, double ny, double L, double left, double right,
@@ -228,11 +206,7 @@ class BlockDatatermSublabel : public Block<T> {
 
  protected:
   BlockDatatermSublabel(size_t row, size_t col, size_t npixels, size_t L, double left, double right);
-  virtual void EvalLocalAdd(T*, T*, const T*, const T*);
-  virtual void EvalAdjointLocalAdd(T*, T*, const T*, const T*);
-  virtual void EvalLocal(T*, T*, const T*, const T*);
-  virtual void EvalAdjointLocal(T*, T*, const T*, const T*);
-  void Product(T* r, const T* x, bool transpose, bool acc);
+  virtual void Product(T* res, const T* rhs, bool transpose, bool accumulate);
   size_t npixels_, L_;
   T delta_;
   std::vector<T> gamma_;          ///< gamma_i = left + i delta, i < L - 1 (formed in double, rounded to T)
@@ -244,7 +218,7 @@ class BlockDatatermSublabel : public Block<T> {
 /// a sparse matrix).  L my mx rows by L ny nx columns.  Arithmetic: prost/linop/conv2d.hpp.  No describe(): the block runs on the
 /// generic paths.  Only O(taps) data is stored: one tap table per direction.
 template <typename T>
-class BlockConv2D : public Block<T> {
+class BlockConv2D : public ProductBlock<T> {
  public:
   /// checks every argument (messages start with "BlockConv2D: "); kernel: ky x kx, column-major; declared_rows / declared_cols < 0:
   /// no size was declared
@@ -260,12 +234,8 @@ class BlockConv2D : public Block<T> {
   size_t taps() const { return ntaps_; }
 
  protected:
-  BlockConv2D(size_t row, size_t col, size_t nrows, size_t ncols) : Block<T>(row, col, nrows, ncols) {}
-  virtual void EvalLocalAdd(T*, T*, const T*, const T*);
-  virtual void EvalAdjointLocalAdd(T*, T*, const T*, const T*);
-  virtual void EvalLocal(T*, T*, const T*, const T*);
-  virtual void EvalAdjointLocal(T*, T*, const T*, const T*);
-  void Product(T* r, const T* x, bool transpose, bool acc);
+  BlockConv2D(size_t row, size_t col, size_t nrows, size_t ncols) : ProductBlock<T>(row, col, nrows, ncols) {}
+  virtual void Product(T* res, const T* rhs, bool transpose, bool accumulate);
   conv2d::Geometry geometry_[2];           ///< the forward [0] and the adjoint [1] direction
   std::vector<T> window_[2];               ///< the window rounded to T, and flipped in both axes
   std::vector<int32_t> words_[2];          ///< the tap tables (conv2d::Tap<T> records) as they are uploaded
@@ -278,7 +248,7 @@ class BlockConv2D : public Block<T> {
 /// differences with the boundary handling of the divergence, the mixed rows weighted by w.  Arithmetic: prost/linop/sym_gradient2d.hpp.
 /// No describe(): the block runs on the generic paths.  Nothing is stored on the device.
 template <typename T>
-class BlockSymGradient2D : public Block<T> {
+class BlockSymGradient2D : public ProductBlock<T> {
  public:
   /// checks every argument (messages start with "BlockSymGradient2D: "); declared_rows / declared_cols < 0: no size was declared
   static BlockSymGradient2D<T>* Create(size_t row, size_t col, double nx, double ny, double L, double w, double declared_rows = -1, double declared_cols = -1);
@@ -292,12 +262,8 @@ class BlockSymGradient2D : public Block<T> {
 
  protected:
   BlockSymGradient2D(size_t row, size_t col, size_t nx, size_t ny, size_t L, double w)
-      : Block<T>(row, col, 3 * L * nx * ny, 2 * L * nx * ny), nx_(nx), ny_(ny), L_(L), w_(w) {}
-  virtual void EvalLocalAdd(T*, T*, const T*, const T*);
-  virtual void EvalAdjointLocalAdd(T*, T*, const T*, const T*);
-  virtual void EvalLocal(T*, T*, const T*, const T*);
-  virtual void EvalAdjointLocal(T*, T*, const T*, const T*);
-  void Product(T* r, const T* x, bool transpose, bool acc);
+      : ProductBlock<T>(row, col, 3 * L * nx * ny, 2 * L * nx * ny), nx_(nx), ny_(ny), L_(L), w_(w) {}
+  virtual void Product(T* res, const T* rhs, bool transpose, bool accumulate);
   double WeightPower(T alpha) const { return sym_gradient2d::WeightPower((double)sym_gradient2d::RoundWeight<T>(w_), (double)alpha); }
   size_t nx_, ny_, L_;
   double w_;               ///< as given; the kernels and the sums round it to T once

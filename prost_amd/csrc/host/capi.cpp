@@ -160,6 +160,13 @@ static const prost_value* cell_at(const prost_value* c, size_t i) {
   if (!c || c->kind != PROST_VALUE_CELL || i >= c->cells.size() || !c->cells[i]) throw Exception("Out-of-bounds access into cell-array.");
   return c->cells[i];
 }
+/// the optional trailing { nrows, ncols } of a matrix-free block's data cells: `base` cells, or `base` + 2 with the size the caller
+/// means the block to have; (-1, -1) where none is declared, `message` for any other count
+static std::pair<double, double> declared_size(const prost_value* d, size_t base, const char* message) {
+  if (!d || d->kind != PROST_VALUE_CELL || (d->cells.size() != base && d->cells.size() != base + 2)) throw Exception(message);
+  if (d->cells.size() == base) return {-1.0, -1.0};
+  return {GetScalarFromCell(d, base), GetScalarFromCell(d, base + 1)};
+}
 static std::vector<const prost_value*> cell_list(const prost_value* c) {
   std::vector<const prost_value*> out;
   if (!c) throw Exception("Tried to run GetCellArray on non-existing array.");
@@ -432,33 +439,27 @@ std::map<std::string, typename Factory<T>::BlockFactory>& Factory<T>::block_reg(
     // the coupling of the sublabel-accurate data term: cells { nx, ny, L, left, right }; a caller that also knows the size it means the
     // block to have appends { nrows, ncols } and gets it checked.  Every argument check is BlockDatatermSublabel<T>::Create's.
     reg["dataterm_sublabel"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
-      if (!d || d->kind != PROST_VALUE_CELL || (d->cells.size() != 5 && d->cells.size() != 7))
-        throw Exception("BlockDatatermSublabel: the data cells are { nx, ny, L, left, right } or { nx, ny, L, left, right, nrows, ncols }.");
-      const bool declared = d->cells.size() == 7;
+      const auto size = declared_size(d, 5, "BlockDatatermSublabel: the data cells are { nx, ny, L, left, right } or { nx, ny, L, left, right, nrows, ncols }.");
       return BlockDatatermSublabel<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), GetScalarFromCell(d, 3),
-                                              GetScalarFromCell(d, 4), declared ? GetScalarFromCell(d, 5) : -1.0, declared ? GetScalarFromCell(d, 6) : -1.0);
+                                              GetScalarFromCell(d, 4), size.first, size.second);
     };
     // 2-D convolution without a matrix: cells { nx, ny, L, kernel (ky x kx full matrix), shape }; a caller that also knows the size it means
     // the block to have appends { nrows, ncols } and gets it checked.  Every argument check is BlockConv2D<T>::Create's.
     reg["conv2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
-      if (!d || d->kind != PROST_VALUE_CELL || (d->cells.size() != 5 && d->cells.size() != 7))
-        throw Exception("BlockConv2D: the data cells are { nx, ny, L, kernel, shape } or { nx, ny, L, kernel, shape, nrows, ncols }.");
+      const auto size = declared_size(d, 5, "BlockConv2D: the data cells are { nx, ny, L, kernel, shape } or { nx, ny, L, kernel, shape, nrows, ncols }.");
       const prost_value* pm = d->cells[3];
       if (!pm || pm->kind != PROST_VALUE_MATRIX) throw Exception("BlockConv2D: the window has to be a full matrix of type single or double.");
       if (!d->cells[4] || d->cells[4]->kind != PROST_VALUE_STRING) throw Exception("BlockConv2D: the shape has to be a string (full, same or valid).");
-      const bool declared = d->cells.size() == 7;
       return BlockConv2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2),
                                     std::vector<double>(pm->data.begin(), pm->data.begin() + pm->rows * pm->cols), pm->rows, pm->cols, d->cells[4]->str,
-                                    declared ? GetScalarFromCell(d, 5) : -1.0, declared ? GetScalarFromCell(d, 6) : -1.0);
+                                    size.first, size.second);
     };
     // the symmetrised gradient of TGV^2 without a matrix: cells { nx, ny, L, w }; a caller that also knows the size it means the block to
     // have appends { nrows, ncols } and gets it checked.  Every argument check is BlockSymGradient2D<T>::Create's.
     reg["sym_gradient2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
-      if (!d || d->kind != PROST_VALUE_CELL || (d->cells.size() != 4 && d->cells.size() != 6))
-        throw Exception("BlockSymGradient2D: the data cells are { nx, ny, L, w } or { nx, ny, L, w, nrows, ncols }.");
-      const bool declared = d->cells.size() == 6;
-      return BlockSymGradient2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), GetScalarFromCell(d, 3),
-                                           declared ? GetScalarFromCell(d, 4) : -1.0, declared ? GetScalarFromCell(d, 5) : -1.0);
+      const auto size = declared_size(d, 4, "BlockSymGradient2D: the data cells are { nx, ny, L, w } or { nx, ny, L, w, nrows, ncols }.");
+      return BlockSymGradient2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), GetScalarFromCell(d, 3), size.first,
+                                           size.second);
     };
     // the dense blocks (factory.cpp:590-601, :694-716): cell 0 is a full matrix, column-major, converted to T.  A sparse cell is refused:
     // the reference would read its value array as if it were the full matrix.

@@ -31,18 +31,18 @@ template class Block<float>;
 template class Block<double>;
 
 // ---- gradient blocks ----
-#define GRAD_IMPL(CLS, FWD, ADJ, CS)                                                                                   \
-  template <typename T> void CLS<T>::EvalLocalAdd(T* r, T*, const T* x, const T*) { CheckHip(Api<T>::FWD(r, x, nx_, ny_, L_, label_first_, 1, CurrentStream()), #FWD); }          \
-  template <typename T> void CLS<T>::EvalAdjointLocalAdd(T* r, T*, const T* x, const T*) { CheckHip(Api<T>::ADJ(r, x, nx_, ny_, L_, label_first_, 1, CurrentStream()), #ADJ); }   \
-  template <typename T> void CLS<T>::EvalLocal(T* r, T*, const T* x, const T*) { CheckHip(Api<T>::FWD(r, x, nx_, ny_, L_, label_first_, 0, CurrentStream()), #FWD); }             \
-  template <typename T> void CLS<T>::EvalAdjointLocal(T* r, T*, const T* x, const T*) { CheckHip(Api<T>::ADJ(r, x, nx_, ny_, L_, label_first_, 0, CurrentStream()), #ADJ); }      \
-  template <typename T> void CLS<T>::row_sums(T* out, T) const { ParallelFor(this->nrows(), [&](size_t b, size_t e) { for (size_t r = b; r < e; r++) out[r] += 2; }); }    \
-  template <typename T> void CLS<T>::col_sums(T* out, T) const { ParallelFor(this->ncols(), [&](size_t b, size_t e) { for (size_t c = b; c < e; c++) out[c] += CS; }); }   \
-  template class CLS<float>;                                                                                           \
-  template class CLS<double>;
-GRAD_IMPL(BlockGradient2D, grad2d_fwd, grad2d_adj, 4)
-GRAD_IMPL(BlockGradient3D, grad3d_fwd, grad3d_adj, 6)
-#undef GRAD_IMPL
+template <typename T, int D>
+void BlockGradient<T, D>::Product(T* r, const T* x, bool transpose, bool accumulate) {
+  const auto fn = D == 2 ? (transpose ? Api<T>::grad2d_adj : Api<T>::grad2d_fwd) : (transpose ? Api<T>::grad3d_adj : Api<T>::grad3d_fwd);
+  const char* name = D == 2 ? (transpose ? "grad2d_adj" : "grad2d_fwd") : (transpose ? "grad3d_adj" : "grad3d_fwd");
+  CheckHip(fn(r, x, nx_, ny_, L_, label_first_, accumulate ? 1 : 0, CurrentStream()), name);
+}
+template <typename T, int D> void BlockGradient<T, D>::row_sums(T* out, T) const { ParallelFor(this->nrows(), [&](size_t b, size_t e) { for (size_t r = b; r < e; r++) out[r] += 2; }); }
+template <typename T, int D> void BlockGradient<T, D>::col_sums(T* out, T) const { ParallelFor(this->ncols(), [&](size_t b, size_t e) { for (size_t c = b; c < e; c++) out[c] += 2 * D; }); }
+template class BlockGradient<float, 2>;
+template class BlockGradient<double, 2>;
+template class BlockGradient<float, 3>;
+template class BlockGradient<double, 3>;
 
 // ---- sparse block ----
 template <typename T>
@@ -56,11 +56,19 @@ BlockSparse<T>* BlockSparse<T>::CreateFromCSC(size_t row, size_t col, int m, int
   BlockSparse<T>* b = new BlockSparse<T>(row, col, m, n);
   b->nnz_ = nnz;
   // the CSC arrays of K are the CSR arrays of K^T; K itself in CSR comes from one transposition
-  b->host_ind_t_ = std::move(ind); b->host_ptr_t_ = std::move(ptr); b->host_val_t_ = std::move(val);
-  b->host_ind_.resize(nnz); b->host_val_.resize(nnz); b->host_ptr_.resize(m + 1);
-  csr2csc<T>(n, m, nnz, b->host_val_t_.data(), b->host_ind_t_.data(), b->host_ptr_t_.data(), b->host_val_.data(),
-             b->host_ind_.data(), b->host_ptr_.data());
+  Side &k = b->side_[0], &kt = b->side_[1];
+  k.rows = m; kt.rows = n;
+  kt.host_ind = std::move(ind); kt.host_ptr = std::move(ptr); kt.host_val = std::move(val);
+  k.host_ind.resize(nnz); k.host_val.resize(nnz); k.host_ptr.resize(m + 1);
+  csr2csc<T>(n, m, nnz, kt.host_val.data(), kt.host_ind.data(), kt.host_ptr.data(), k.host_val.data(), k.host_ind.data(), k.host_ptr.data());
   return b;
+}
+template <typename V>
+template <typename T>
+T CsrSide<V>::AbsPowSum(size_t row, T alpha) const {
+  T sum = 0;
+  for (int32_t i = host_ptr[row]; i < host_ptr[row + 1]; i++) sum += std::pow(std::abs(host_val[i]), alpha);
+  return sum;
 }
 // Rows of a CSR matrix as repeated (column - row, value) sequences.  Returns false -- the matrix stays CSR -- when it is small (< 256
 // rows), when its rows are not made of few sequences (more than a quarter of up to 4096 sampled rows differ; > 4096 sequences in all, or
@@ -157,6 +165,8 @@ template <typename T> void BlockSparse<T>::SetStencilRecognition(bool on) { g_st
 template <typename T>
 void BlockSparse<T>::DetectGradient2D() {
   grad_nx_ = grad_ny_ = grad_L_ = 0;
+  const std::vector<int32_t>&host_ptr_ = side_[0].host_ptr, &host_ind_ = side_[0].host_ind;
+  const std::vector<T>& host_val_ = side_[0].host_val;
   const size_t m = this->nrows(), n = this->ncols();
   if (!g_stencil_recognition || m != 2 * n || n < 4 || host_ptr_.size() != m + 1) return;
   if (host_ptr_[1] - host_ptr_[0] != 2 || host_ind_[0] != 0 || host_val_[0] != (T)-1 || host_val_[1] != (T)1) return;
@@ -189,25 +199,38 @@ template <typename T> bool BlockSparse<T>::pattern_compression() { return g_spar
 
 template <typename T>
 void BlockSparse<T>::Initialize() {
-  pat_.on = pat_t_.on = false;
-  auto build = [&](RowPatterns& p, size_t nrows, const std::vector<int32_t>& hp, const std::vector<int32_t>& hi, const std::vector<T>& hv) {
+  for (Side& s : side_) s.pat.on = false;
+  DetectGradient2D();
+  DetectPointwise();
+  for (Side& s : side_) {
     HostRowPatterns<T> h;
     // (offsets from the row number first -- 2 bytes per row; then from the row's first column -- 6 bytes per row, for matrices that map
     // between different geometries: convmtx2 of example_deblurring.m)
-    if (!g_sparse_patterns || !(BuildRowPatterns<T>(nrows, hp, hi, hv, h) || BuildRowPatterns<T>(nrows, hp, hi, hv, h, true))) return;
+    if (!g_sparse_patterns || !(BuildRowPatterns<T>(s.rows, s.host_ptr, s.host_ind, s.host_val, h) || BuildRowPatterns<T>(s.rows, s.host_ptr, s.host_ind, s.host_val, h, true))) continue;
+    RowPatterns& p = s.pat;
     p.ids = h.ids; p.pptr = h.pptr; p.rel = h.rel; p.val = h.val;
     p.anchor.clear();
     if (!h.anchor.empty()) p.anchor = h.anchor;
     p.count = h.pptr.size() - 1;
     p.on = true;
-  };
-  DetectGradient2D();
-  DetectPointwise();
-  build(pat_, this->nrows(), host_ptr_, host_ind_, host_val_);
-  build(pat_t_, this->ncols(), host_ptr_t_, host_ind_t_, host_val_t_);
+  }
   // the CSR arrays of a product that runs from row patterns stay on the host (a 4096^2 gradient: 0.5 GB of upload each)
-  if (!pat_.on) { ind_ = host_ind_; ptr_ = host_ptr_; val_ = host_val_; }
-  if (!pat_t_.on) { ind_t_ = host_ind_t_; ptr_t_ = host_ptr_t_; val_t_ = host_val_t_; }
+  for (Side& s : side_) if (!s.pat.on) s.Upload();
+}
+template <typename T>
+bool BlockSparse<T>::describe(BlockDesc& d) const {
+  if (nnz_ == 0) return false;
+  for (const Side& s : side_) if (!s.pat.on && s.val.size() != nnz_) return false;          // before Initialize()
+  d.kind = BlockDesc::kSparse; d.nnz = nnz_;
+  auto fill = [](const Side& s, const void*& val, const int32_t*& ptr, const int32_t*& ind, const uint16_t*& ids, const int32_t*& pptr, const int32_t*& rel, const void*& pval,
+                 const int32_t*& anchor) {
+    if (s.pat.on) { ids = s.pat.ids.data(); pptr = s.pat.pptr.data(); rel = s.pat.rel.data(); pval = s.pat.val.data(); anchor = s.pat.anchor.size() ? s.pat.anchor.data() : nullptr; }
+    else { val = s.val.data(); ptr = s.ptr.data(); ind = s.ind.data(); }
+  };
+  fill(side_[0], d.val, d.ptr, d.ind, d.ids, d.pptr, d.rel, d.pval, d.anchor);
+  fill(side_[1], d.val_t, d.ptr_t, d.ind_t, d.ids_t, d.pptr_t, d.rel_t, d.pval_t, d.anchor_t);
+  d.pointwise_planes = pointwise_planes_;
+  return true;
 }
 /// K couples the channels of one pixel: nrows x (L nrows), row i = L entries at columns i, i + nrows, ..., i + (L - 1) nrows -- the
 /// shape of [diag(Ix) diag(Iy)] (a warp / data-term matrix of a multi-channel model).  The two-launch CG rounds of the ADMM backend
@@ -215,6 +238,7 @@ void BlockSparse<T>::Initialize() {
 template <typename T>
 void BlockSparse<T>::DetectPointwise() {
   pointwise_planes_ = 0;
+  const std::vector<int32_t>&host_ptr_ = side_[0].host_ptr, &host_ind_ = side_[0].host_ind;
   const size_t m = this->nrows(), n = this->ncols();
   if (m == 0 || n % m != 0 || host_ptr_.size() != m + 1) return;
   const size_t L = n / m;
@@ -231,25 +255,17 @@ void BlockSparse<T>::DetectPointwise() {
 }
 template <typename T>
 void BlockSparse<T>::Release() {
-  ind_.clear(); ptr_.clear(); val_.clear(); ind_t_.clear(); ptr_t_.clear(); val_t_.clear();
-  for (RowPatterns* p : {&pat_, &pat_t_}) { p->on = false; p->ids.clear(); p->pptr.clear(); p->rel.clear(); p->val.clear(); p->anchor.clear(); }
+  for (Side& s : side_) s.Clear();
+  for (Side& s : side_) { RowPatterns& p = s.pat; p.on = false; p.ids.clear(); p.pptr.clear(); p.rel.clear(); p.val.clear(); p.anchor.clear(); }
 }
-template <typename T>
-T BlockSparse<T>::row_sum(size_t row, T alpha) const {
-  T sum = 0;
-  for (int32_t i = host_ptr_[row]; i < host_ptr_[row + 1]; i++) sum += std::pow(std::abs(host_val_[i]), alpha);
-  return sum;
-}
-template <typename T>
-T BlockSparse<T>::col_sum(size_t col, T alpha) const {
-  T sum = 0;
-  for (int32_t i = host_ptr_t_[col]; i < host_ptr_t_[col + 1]; i++) sum += std::pow(std::abs(host_val_t_[i]), alpha);
-  return sum;
-}
+template <typename T> T BlockSparse<T>::row_sum(size_t row, T alpha) const { return side_[0].AbsPowSum(row, alpha); }
+template <typename T> T BlockSparse<T>::col_sum(size_t col, T alpha) const { return side_[1].AbsPowSum(col, alpha); }
 // |v|^alpha: alpha == 1 (the default scaling, both for rows and for columns: 2 - alpha == 1) needs no pow -- pow(x, 1) == x
 template <typename T>
-static void csr_abs_pow_sums(T* out, size_t n, const std::vector<int32_t>& ptr, const std::vector<T>& val, T alpha) {
-  ParallelFor(n, [&](size_t lo, size_t hi) {
+static void csr_abs_pow_sums(T* out, const CsrSide<T>& s, T alpha) {
+  const std::vector<int32_t>& ptr = s.host_ptr;
+  const std::vector<T>& val = s.host_val;
+  ParallelFor(s.rows, [&](size_t lo, size_t hi) {
     for (size_t r = lo; r < hi; r++) {
       T sum = 0;
       if (alpha == (T)1) { for (int32_t i = ptr[r]; i < ptr[r + 1]; i++) sum += std::abs(val[i]); }
@@ -258,46 +274,30 @@ static void csr_abs_pow_sums(T* out, size_t n, const std::vector<int32_t>& ptr, 
     }
   });
 }
-template <typename T> void BlockSparse<T>::row_sums(T* out, T alpha) const { csr_abs_pow_sums<T>(out, this->nrows(), host_ptr_, host_val_, alpha); }
-template <typename T> void BlockSparse<T>::col_sums(T* out, T alpha) const { csr_abs_pow_sums<T>(out, this->ncols(), host_ptr_t_, host_val_t_, alpha); }
+template <typename T> void BlockSparse<T>::row_sums(T* out, T alpha) const { csr_abs_pow_sums<T>(out, side_[0], alpha); }
+template <typename T> void BlockSparse<T>::col_sums(T* out, T alpha) const { csr_abs_pow_sums<T>(out, side_[1], alpha); }
 template <typename T>
 size_t BlockSparse<T>::gpu_mem_amount() const {
   size_t bytes = 0;
-  if (!pat_.on) bytes += nnz_ * (sizeof(int32_t) + sizeof(T)) + (this->nrows() + 1) * sizeof(int32_t);
-  if (!pat_t_.on) bytes += nnz_ * (sizeof(int32_t) + sizeof(T)) + (this->ncols() + 1) * sizeof(int32_t);
-  for (const RowPatterns* p : {&pat_, &pat_t_}) bytes += p->ids.size() * sizeof(uint16_t) + (p->pptr.size() + p->rel.size() + p->anchor.size()) * sizeof(int32_t) + p->val.size() * sizeof(T);
+  for (const Side& s : side_) if (!s.pat.on) bytes += nnz_ * (sizeof(int32_t) + sizeof(T)) + (s.rows + 1) * sizeof(int32_t);
+  for (const Side& s : side_) bytes += s.pat.ids.size() * sizeof(uint16_t) + (s.pat.pptr.size() + s.pat.rel.size() + s.pat.anchor.size()) * sizeof(int32_t) + s.pat.val.size() * sizeof(T);
   return bytes;
 }
 template <typename T>
-void BlockSparse<T>::PatternProduct(const RowPatterns& p, T* r, const T* x, size_t rows, int acc) {
+void BlockSparse<T>::PatternProduct(const Side& s, T* r, const T* x, int acc) {
+  const RowPatterns& p = s.pat;
   if (p.anchor.size())
-    CheckHip(Api<T>::pattern_spmv_anchored(r, x, rows, p.ids.data(), p.anchor.data(), p.pptr.data(), p.rel.data(), p.val.data(), (int)p.pptr.size() - 1, (int)p.rel.size(), acc, CurrentStream()), "pattern_spmv_anchored");
+    CheckHip(Api<T>::pattern_spmv_anchored(r, x, s.rows, p.ids.data(), p.anchor.data(), p.pptr.data(), p.rel.data(), p.val.data(), (int)p.pptr.size() - 1, (int)p.rel.size(), acc, CurrentStream()), "pattern_spmv_anchored");
   else
-    CheckHip(Api<T>::pattern_spmv(r, x, rows, p.ids.data(), p.pptr.data(), p.rel.data(), p.val.data(), (int)p.pptr.size() - 1, (int)p.rel.size(), acc, CurrentStream()), "pattern_spmv");
+    CheckHip(Api<T>::pattern_spmv(r, x, s.rows, p.ids.data(), p.pptr.data(), p.rel.data(), p.val.data(), (int)p.pptr.size() - 1, (int)p.rel.size(), acc, CurrentStream()), "pattern_spmv");
 }
 template <typename T>
-void BlockSparse<T>::EvalLocalAdd(T* r, T*, const T* x, const T*) {
-  if (!pat_.on && val_.size() != nnz_ && nnz_) throw Exception("BlockSparse used before Initialize().");
-  if (pat_.on) { PatternProduct(pat_, r, x, this->nrows(), 1); return; }
-  CheckHip(Api<T>::csr_spmv_acc(r, x, this->nrows(), nnz_, val_.data(), ptr_.data(), ind_.data(), CurrentStream()), "csr_spmv_acc");
-}
-template <typename T>
-void BlockSparse<T>::EvalAdjointLocalAdd(T* r, T*, const T* x, const T*) {
-  if (!pat_t_.on && val_t_.size() != nnz_ && nnz_) throw Exception("BlockSparse used before Initialize().");
-  if (pat_t_.on) { PatternProduct(pat_t_, r, x, this->ncols(), 1); return; }
-  CheckHip(Api<T>::csr_spmv_acc(r, x, this->ncols(), nnz_, val_t_.data(), ptr_t_.data(), ind_t_.data(), CurrentStream()), "csr_spmv_acc");
-}
-template <typename T>
-void BlockSparse<T>::EvalLocal(T* r, T*, const T* x, const T*) {
-  if (!pat_.on && val_.size() != nnz_ && nnz_) throw Exception("BlockSparse used before Initialize().");
-  if (pat_.on) { PatternProduct(pat_, r, x, this->nrows(), 0); return; }
-  CheckHip(Api<T>::csr_spmv(r, x, this->nrows(), nnz_, val_.data(), ptr_.data(), ind_.data(), CurrentStream()), "csr_spmv");
-}
-template <typename T>
-void BlockSparse<T>::EvalAdjointLocal(T* r, T*, const T* x, const T*) {
-  if (!pat_t_.on && val_t_.size() != nnz_ && nnz_) throw Exception("BlockSparse used before Initialize().");
-  if (pat_t_.on) { PatternProduct(pat_t_, r, x, this->ncols(), 0); return; }
-  CheckHip(Api<T>::csr_spmv(r, x, this->ncols(), nnz_, val_t_.data(), ptr_t_.data(), ind_t_.data(), CurrentStream()), "csr_spmv");
+void BlockSparse<T>::Product(T* r, const T* x, bool transpose, bool accumulate) {
+  const Side& s = side_[transpose];
+  if (!s.pat.on && s.val.size() != nnz_ && nnz_) throw Exception("BlockSparse used before Initialize().");
+  if (s.pat.on) { PatternProduct(s, r, x, accumulate ? 1 : 0); return; }
+  if (accumulate) CheckHip(Api<T>::csr_spmv_acc(r, x, s.rows, nnz_, s.val.data(), s.ptr.data(), s.ind.data(), CurrentStream()), "csr_spmv_acc");
+  else CheckHip(Api<T>::csr_spmv(r, x, s.rows, nnz_, s.val.data(), s.ptr.data(), s.ind.data(), CurrentStream()), "csr_spmv");
 }
 template class BlockSparse<float>;
 template class BlockSparse<double>;
@@ -307,61 +307,38 @@ template <typename T>
 BlockKronSparse<T>* BlockKronSparse<T>::CreateFromCSC(bool id_first, size_t row, size_t col, size_t diaglength, int m, int n, int nnz,
                                                       const std::vector<T>& val, const std::vector<int32_t>& ptr, const std::vector<int32_t>& ind) {
   BlockKronSparse<T>* b = new BlockKronSparse<T>(row, col, (size_t)m * diaglength, (size_t)n * diaglength);
-  b->id_first_ = id_first; b->diaglength_ = diaglength; b->mat_nnz_ = nnz; b->mat_nrows_ = m; b->mat_ncols_ = n;
-  b->host_ind_t_ = ind; b->host_ptr_t_ = ptr; b->host_val_t_ = std::vector<float>(val.begin(), val.end());     // block_sparse_kron_id.cu:77-79
-  b->host_ind_.resize(nnz); b->host_val_.resize(nnz); b->host_ptr_.resize(m + 1);
-  csr2csc<float>(n, m, nnz, b->host_val_t_.data(), b->host_ind_t_.data(), b->host_ptr_t_.data(), b->host_val_.data(), b->host_ind_.data(),
-                 b->host_ptr_.data());
+  b->id_first_ = id_first; b->diaglength_ = diaglength; b->mat_nnz_ = nnz;
+  CsrSide<float> &k = b->side_[0], &kt = b->side_[1];
+  k.rows = m; kt.rows = n;
+  kt.host_ind = ind; kt.host_ptr = ptr; kt.host_val = std::vector<float>(val.begin(), val.end());     // block_sparse_kron_id.cu:77-79
+  k.host_ind.resize(nnz); k.host_val.resize(nnz); k.host_ptr.resize(m + 1);
+  csr2csc<float>(n, m, nnz, kt.host_val.data(), kt.host_ind.data(), kt.host_ptr.data(), k.host_val.data(), k.host_ind.data(), k.host_ptr.data());
   return b;
 }
+template <typename T> void BlockKronSparse<T>::Initialize() { for (auto& s : side_) s.Upload(); }
+template <typename T> void BlockKronSparse<T>::Release() { for (auto& s : side_) s.Clear(); }
 template <typename T>
-void BlockKronSparse<T>::Initialize() {
-  ind_ = host_ind_; ptr_ = host_ptr_; val_ = host_val_;
-  ind_t_ = host_ind_t_; ptr_t_ = host_ptr_t_; val_t_ = host_val_t_;
-}
+T BlockKronSparse<T>::row_sum(size_t row, T alpha) const { return side_[0].AbsPowSum(id_first_ ? row % side_[0].rows : row / diaglength_, alpha); }
 template <typename T>
-void BlockKronSparse<T>::Release() { ind_.clear(); ptr_.clear(); val_.clear(); ind_t_.clear(); ptr_t_.clear(); val_t_.clear(); }
-template <typename T>
-T BlockKronSparse<T>::row_sum(size_t row, T alpha) const {
-  row = id_first_ ? row % mat_nrows_ : row / diaglength_;
-  T sum = 0;
-  for (int32_t i = host_ptr_[row]; i < host_ptr_[row + 1]; i++) sum += std::pow(std::abs(host_val_[i]), alpha);
-  return sum;
-}
-template <typename T>
-T BlockKronSparse<T>::col_sum(size_t col, T alpha) const {
-  col = id_first_ ? col % mat_ncols_ : col / diaglength_;
-  T sum = 0;
-  for (int32_t i = host_ptr_t_[col]; i < host_ptr_t_[col + 1]; i++) sum += std::pow(std::abs(host_val_t_[i]), alpha);
-  return sum;
-}
+T BlockKronSparse<T>::col_sum(size_t col, T alpha) const { return side_[1].AbsPowSum(id_first_ ? col % side_[1].rows : col / diaglength_, alpha); }
 template <typename T>
 size_t BlockKronSparse<T>::gpu_mem_amount() const {
-  return (host_ind_.size() + host_ind_t_.size() + host_ptr_.size() + host_ptr_t_.size()) * sizeof(int32_t) + (host_val_.size() + host_val_t_.size()) * sizeof(T);
+  size_t bytes = 0;
+  for (const auto& s : side_) bytes += (s.host_ind.size() + s.host_ptr.size()) * sizeof(int32_t) + s.host_val.size() * sizeof(T);
+  return bytes;
 }
 template <typename T>
-void BlockKronSparse<T>::EvalLocalAdd(T* r, T*, const T* x, const T*) {
-  if (ptr_.size() != host_ptr_.size()) throw Exception("BlockKronSparse used before Initialize().");
-  if (id_first_) CheckHip(Api<T>::id_kron_sparse_acc(r, x, diaglength_, mat_nrows_, mat_ncols_, val_.data(), ptr_.data(), ind_.data(), CurrentStream()), "id_kron_sparse_acc");
-  else CheckHip(Api<T>::sparse_kron_id_acc(r, x, diaglength_, mat_nrows_, val_.data(), ptr_.data(), ind_.data(), CurrentStream()), "sparse_kron_id_acc");
-}
-template <typename T>
-void BlockKronSparse<T>::EvalAdjointLocalAdd(T* r, T*, const T* x, const T*) {
-  if (ptr_t_.size() != host_ptr_t_.size()) throw Exception("BlockKronSparse used before Initialize().");
-  if (id_first_) CheckHip(Api<T>::id_kron_sparse_acc(r, x, diaglength_, mat_ncols_, mat_nrows_, val_t_.data(), ptr_t_.data(), ind_t_.data(), CurrentStream()), "id_kron_sparse_acc");
-  else CheckHip(Api<T>::sparse_kron_id_acc(r, x, diaglength_, mat_ncols_, val_t_.data(), ptr_t_.data(), ind_t_.data(), CurrentStream()), "sparse_kron_id_acc");
-}
-template <typename T>
-void BlockKronSparse<T>::EvalLocal(T* r, T*, const T* x, const T*) {
-  if (ptr_.size() != host_ptr_.size()) throw Exception("BlockKronSparse used before Initialize().");
-  if (id_first_) CheckHip(Api<T>::id_kron_sparse(r, x, diaglength_, mat_nrows_, mat_ncols_, val_.data(), ptr_.data(), ind_.data(), CurrentStream()), "id_kron_sparse");
-  else CheckHip(Api<T>::sparse_kron_id(r, x, diaglength_, mat_nrows_, val_.data(), ptr_.data(), ind_.data(), CurrentStream()), "sparse_kron_id");
-}
-template <typename T>
-void BlockKronSparse<T>::EvalAdjointLocal(T* r, T*, const T* x, const T*) {
-  if (ptr_t_.size() != host_ptr_t_.size()) throw Exception("BlockKronSparse used before Initialize().");
-  if (id_first_) CheckHip(Api<T>::id_kron_sparse(r, x, diaglength_, mat_ncols_, mat_nrows_, val_t_.data(), ptr_t_.data(), ind_t_.data(), CurrentStream()), "id_kron_sparse");
-  else CheckHip(Api<T>::sparse_kron_id(r, x, diaglength_, mat_ncols_, val_t_.data(), ptr_t_.data(), ind_t_.data(), CurrentStream()), "sparse_kron_id");
+void BlockKronSparse<T>::Product(T* r, const T* x, bool transpose, bool accumulate) {
+  const CsrSide<float>& s = side_[transpose];
+  const size_t mat_cols = side_[!transpose].rows;
+  if (s.ptr.size() != s.host_ptr.size()) throw Exception("BlockKronSparse used before Initialize().");
+  if (id_first_) {
+    const auto fn = accumulate ? Api<T>::id_kron_sparse_acc : Api<T>::id_kron_sparse;
+    CheckHip(fn(r, x, diaglength_, s.rows, mat_cols, s.val.data(), s.ptr.data(), s.ind.data(), CurrentStream()), accumulate ? "id_kron_sparse_acc" : "id_kron_sparse");
+  } else {
+    const auto fn = accumulate ? Api<T>::sparse_kron_id_acc : Api<T>::sparse_kron_id;
+    CheckHip(fn(r, x, diaglength_, s.rows, s.val.data(), s.ptr.data(), s.ind.data(), CurrentStream()), accumulate ? "sparse_kron_id_acc" : "sparse_kron_id");
+  }
 }
 template class BlockKronSparse<float>;
 template class BlockKronSparse<double>;
@@ -404,10 +381,6 @@ void BlockDense<T>::Product(T* r, const T* x, bool transpose, bool acc) {
   if (acc) CheckHip(Api<T>::dense_gemv_acc(r, x, this->nrows(), this->ncols(), data_.data(), transpose ? 1 : 0, ws, CurrentStream()), "dense_gemv_acc");
   else CheckHip(Api<T>::dense_gemv(r, x, this->nrows(), this->ncols(), data_.data(), transpose ? 1 : 0, ws, CurrentStream()), "dense_gemv");
 }
-template <typename T> void BlockDense<T>::EvalLocalAdd(T* r, T*, const T* x, const T*) { Product(r, x, false, true); }
-template <typename T> void BlockDense<T>::EvalAdjointLocalAdd(T* r, T*, const T* x, const T*) { Product(r, x, true, true); }
-template <typename T> void BlockDense<T>::EvalLocal(T* r, T*, const T* x, const T*) { Product(r, x, false, false); }
-template <typename T> void BlockDense<T>::EvalAdjointLocal(T* r, T*, const T* x, const T*) { Product(r, x, true, false); }
 template class BlockDense<float>;
 template class BlockDense<double>;
 
@@ -446,10 +419,6 @@ void BlockKronDense<T>::Product(T* r, const T* x, bool transpose, bool acc) {
   auto fn = id_first_ ? (acc ? Api<T>::id_kron_dense_acc : Api<T>::id_kron_dense) : (acc ? Api<T>::dense_kron_id_acc : Api<T>::dense_kron_id);
   CheckHip(fn(r, x, diaglength_, mat_nrows_, mat_ncols_, data_.data(), transpose ? 1 : 0, CurrentStream()), id_first_ ? "id_kron_dense" : "dense_kron_id");
 }
-template <typename T> void BlockKronDense<T>::EvalLocalAdd(T* r, T*, const T* x, const T*) { Product(r, x, false, true); }
-template <typename T> void BlockKronDense<T>::EvalAdjointLocalAdd(T* r, T*, const T* x, const T*) { Product(r, x, true, true); }
-template <typename T> void BlockKronDense<T>::EvalLocal(T* r, T*, const T* x, const T*) { Product(r, x, false, false); }
-template <typename T> void BlockKronDense<T>::EvalAdjointLocal(T* r, T*, const T* x, const T*) { Product(r, x, true, false); }
 template class BlockKronDense<float>;
 template class BlockKronDense<double>;
 
@@ -474,7 +443,7 @@ BlockDatatermSublabel<T>* BlockDatatermSublabel<T>::Create(size_t row, size_t co
 }
 template <typename T>
 BlockDatatermSublabel<T>::BlockDatatermSublabel(size_t row, size_t col, size_t npixels, size_t L, double left, double right)
-    : Block<T>(row, col, 2 * npixels * (L - 1), 2 * npixels * (L - 1)), npixels_(npixels), L_(L), gamma_(L - 1) {
+    : ProductBlock<T>(row, col, 2 * npixels * (L - 1), 2 * npixels * (L - 1)), npixels_(npixels), L_(L), gamma_(L - 1) {
   dataterm_sublabel::Labels<T>(L, left, right, delta_, gamma_.data());
 }
 template <typename T>
@@ -515,10 +484,6 @@ void BlockDatatermSublabel<T>::Product(T* r, const T* x, bool transpose, bool ac
   CheckHip(Api<T>::linop_dataterm_sublabel(r, x, npixels_, L_, d_gamma_.data(), (double)delta_, transpose ? 1 : 0, acc ? 1 : 0, CurrentStream()),
            "linop_dataterm_sublabel");
 }
-template <typename T> void BlockDatatermSublabel<T>::EvalLocalAdd(T* r, T*, const T* x, const T*) { Product(r, x, false, true); }
-template <typename T> void BlockDatatermSublabel<T>::EvalAdjointLocalAdd(T* r, T*, const T* x, const T*) { Product(r, x, true, true); }
-template <typename T> void BlockDatatermSublabel<T>::EvalLocal(T* r, T*, const T* x, const T*) { Product(r, x, false, false); }
-template <typename T> void BlockDatatermSublabel<T>::EvalAdjointLocal(T* r, T*, const T* x, const T*) { Product(r, x, true, false); }
 template class BlockDatatermSublabel<float>;
 template class BlockDatatermSublabel<double>;
 
@@ -600,10 +565,6 @@ void BlockConv2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
                           acc ? 1 : 0, CurrentStream()),
            "conv2d");
 }
-template <typename T> void BlockConv2D<T>::EvalLocalAdd(T* r, T*, const T* x, const T*) { Product(r, x, false, true); }
-template <typename T> void BlockConv2D<T>::EvalAdjointLocalAdd(T* r, T*, const T* x, const T*) { Product(r, x, true, true); }
-template <typename T> void BlockConv2D<T>::EvalLocal(T* r, T*, const T* x, const T*) { Product(r, x, false, false); }
-template <typename T> void BlockConv2D<T>::EvalAdjointLocal(T* r, T*, const T* x, const T*) { Product(r, x, true, false); }
 template class BlockConv2D<float>;
 template class BlockConv2D<double>;
 
@@ -646,10 +607,6 @@ template <typename T>
 void BlockSymGradient2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
   CheckHip(Api<T>::linop_sym_gradient2d(r, x, nx_, ny_, L_, w_, transpose ? 1 : 0, acc ? 1 : 0, CurrentStream()), "linop_sym_gradient2d");
 }
-template <typename T> void BlockSymGradient2D<T>::EvalLocalAdd(T* r, T*, const T* x, const T*) { Product(r, x, false, true); }
-template <typename T> void BlockSymGradient2D<T>::EvalAdjointLocalAdd(T* r, T*, const T* x, const T*) { Product(r, x, true, true); }
-template <typename T> void BlockSymGradient2D<T>::EvalLocal(T* r, T*, const T* x, const T*) { Product(r, x, false, false); }
-template <typename T> void BlockSymGradient2D<T>::EvalAdjointLocal(T* r, T*, const T* x, const T*) { Product(r, x, true, false); }
 template class BlockSymGradient2D<float>;
 template class BlockSymGradient2D<double>;
 

@@ -4,30 +4,15 @@ tests/host/dataterm_sublabel_harness.cpp is a stand-alone program (plain g++, no
 plain loop over the pixels, for fp32 and fp64, against a long-double evaluation of the matrix: |got - exact| <= 1.01 (k + 2) u (|K| |x|)
 componentwise, <K x, y> = <x, K^T y> within the same bound, the accumulating and in-place forms and a two-pixel access bit for bit
 against the plain march.  Shapes include k = 1 and N = 1; every buffer has exactly its size."""
-import os
 import re
-import shutil
-import subprocess
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "dataterm_sublabel_harness.cpp")
+import host_harness
 
 
 def test_marches_and_sums_under_sanitizers(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / "dataterm_sublabel_harness")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-I" + os.path.join(ROOT, "include"), SRC, "-o", exe]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
-    print(r.stdout)
-    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-4000:])
-    lines = r.stdout.strip().splitlines()
-    assert lines[-1] == "ok" and "FAIL" not in r.stdout
+    stdout = host_harness.run_sanitized("dataterm_sublabel_harness", tmp_path)
+    lines = stdout.strip().splitlines()
+    assert lines[-1] == "ok" and "FAIL" not in stdout
     for t in ("fp32", "fp64"):
         got = [l for l in lines if re.match(r"N=\d+ L=\d+ .* %s: worst error / bound [0-9.]+, within$" % t, l)]
         assert len(got) == 9, (t, len(got))
@@ -35,4 +20,3 @@ def test_marches_and_sums_under_sanitizers(tmp_path):
         # the check has teeth: some shape comes near its bound's order of magnitude, none passes it
         ratios = [float(re.search(r"bound ([0-9.]+),", l).group(1)) for l in got]
         assert max(ratios) <= 1.0 and max(ratios) > 0.01, ratios
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]

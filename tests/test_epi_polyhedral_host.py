@@ -5,16 +5,10 @@ fp32 and fp64, dim 2 .. 4, random lists and the degenerate ones (duplicate, para
 Its own brute force in long double is the truth; every case has to print `within` (max(4 e_T, 32 eps_T), e_T from an elimination in
 T on the true active set), and no point may reach the step cap, whose constants are those of prost_hip_epi_polyhedral_plan."""
 import ctypes as C
-import os
-import shutil
 import subprocess
 
-import pytest
-
+import host_harness
 from prost_amd import _hip
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "epi_polyhedral_harness.cpp")
 CASES = ["random", "random1000", "duplicate", "parallel", "linf_pyramid", "l1_pyramid", "zero_rows"]
 
 
@@ -28,25 +22,15 @@ def plan_caps():
 
 
 def test_active_set_projection_under_sanitizers(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
     ca, cb = plan_caps()
-    exe = str(tmp_path / "epi_polyhedral_harness")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-I" + os.path.join(ROOT, "include"), SRC, "-o", exe]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe, str(ca), str(cb)], capture_output=True, text=True, timeout=600, env=env)
-    print(r.stdout)
-    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-4000:])
-    lines = r.stdout.strip().splitlines()
-    assert lines[-1] == "ok" and "FAIL" not in r.stdout
+    stdout = host_harness.run_sanitized("epi_polyhedral_harness", tmp_path, [str(ca), str(cb)])
+    lines = stdout.strip().splitlines()
+    assert lines[-1] == "ok" and "FAIL" not in stdout
     assert ", reached the cap 0, failures 0" in lines[-2]
     for t in ("fp32", "fp64"):
         for dim in (2, 3, 4):
             for name in CASES:
                 assert any(l.startswith("%s %s dim=%d " % (name, t, dim)) and l.endswith("within") for l in lines), (name, t, dim)
             assert "empty %s dim=%d: within" % (t, dim) in lines
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
     # other cap constants are refused: the harness and the plan cannot drift apart unnoticed
-    assert subprocess.run([exe, str(ca + 1), str(cb)], capture_output=True, text=True, timeout=60, env=env).returncode == 1
+    assert subprocess.run([str(tmp_path / "epi_polyhedral_harness"), str(ca + 1), str(cb)], capture_output=True, text=True, timeout=60, env=host_harness.sanitizer_env()).returncode == 1

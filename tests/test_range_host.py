@@ -4,16 +4,10 @@ functions prost_amd/csrc/kernels_prox_range.hip calls lane by lane -- in loops: 
 prost_hip_range_potrs_plan, for fp32 and fp64 and n in {1, 2, NB - 1, NB, NB + 1, 2 NB + 1}.  The exact family must come out bit for bit;
 the tolerance family within max(4 e_T, 32 eps_T) of an unblocked loop in long double, e_T being the error of that loop in T."""
 import ctypes as C
-import os
-import shutil
 import subprocess
 
-import pytest
-
+import host_harness
 from prost_amd import _hip
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "potrs_blocks_harness.cpp")
 
 
 def plan_nb():
@@ -26,25 +20,15 @@ def plan_nb():
 
 
 def test_blocked_factorisation_and_sweeps_under_sanitizers(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
     nb = plan_nb()
-    exe = str(tmp_path / "potrs_blocks_harness")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-I" + os.path.join(ROOT, "include"), SRC, "-o", exe]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe, str(nb)], capture_output=True, text=True, timeout=600, env=env)
-    print(r.stdout)
-    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-4000:])
-    lines = r.stdout.strip().splitlines()
-    assert lines[-1] == "ok" and "FAIL" not in r.stdout
+    stdout = host_harness.run_sanitized("potrs_blocks_harness", tmp_path, [str(nb)])
+    lines = stdout.strip().splitlines()
+    assert lines[-1] == "ok" and "FAIL" not in stdout
     sizes = [1, 2, nb - 1, nb, nb + 1, 2 * nb + 1]
     for t in ("fp32", "fp64"):
         for n in sizes:
             assert "exact %s n=%d: equal" % (t, n) in lines, (t, n)
             assert any(l.startswith("tolerance %s n=%d:" % (t, n)) and l.endswith("within") for l in lines), (t, n)
     assert "indefinite: pivot 1" in lines
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
     # a wrong NB is refused: the harness and the plan cannot drift apart unnoticed
-    assert subprocess.run([exe, str(nb + 1)], capture_output=True, text=True, timeout=60, env=env).returncode == 1
+    assert subprocess.run([str(tmp_path / "potrs_blocks_harness"), str(nb + 1)], capture_output=True, text=True, timeout=60, env=host_harness.sanitizer_env()).returncode == 1

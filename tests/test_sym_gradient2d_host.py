@@ -7,30 +7,15 @@ fp32 and fp64 and w = 0.5 and sqrt(1/2), against the explicit entry list summed 
 res0 + plain, every W, strip width and chunk width bit for bit against W = 1, both marches on unit vectors equal to the entry list and
 its transpose entry for entry, the row and column sums within (t + 8) eps_T of the sums of the entries (w = 0.5, alpha = 1: equal).
 Shapes: the list of tests/test_gpu_sym_gradient2d.py; every buffer has exactly its size."""
-import os
 import re
-import shutil
-import subprocess
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "sym_gradient2d_harness.cpp")
+import host_harness
 
 
 def test_marches_and_sums_under_sanitizers(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / "sym_gradient2d_harness")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-I" + os.path.join(ROOT, "include"), SRC, "-o", exe]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
-    print(r.stdout)
-    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-4000:])
-    lines = r.stdout.strip().splitlines()
-    assert lines[-1] == "ok" and "FAIL" not in r.stdout
+    stdout = host_harness.run_sanitized("sym_gradient2d_harness", tmp_path)
+    lines = stdout.strip().splitlines()
+    assert lines[-1] == "ok" and "FAIL" not in stdout
     for t in ("fp32", "fp64"):
         got = [l for l in lines if re.match(r"\d+x\d+x\d+ w 0\.(500|707) %s: \d+ entries, worst error / bound [0-9.]+, within$" % t, l)]
         assert len(got) == 40, (t, len(got))               # twenty shapes, two weights
@@ -41,4 +26,3 @@ def test_marches_and_sums_under_sanitizers(tmp_path):
         assert max(ratios) <= 1.0 and max(ratios) > 0.01, ratios
     m = re.match(r"marches equal to the matrix and its transpose entry for entry in (\d+) runs$", lines[-2])
     assert m and int(m.group(1)) >= 20, lines[-2]
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
