@@ -5,6 +5,7 @@
 #include "prost/device_vector.hpp"
 #include "prost/linop/block.hpp"
 #include "prost/linop/conv2d.hpp"
+#include "prost/linop/conv2d_strided.hpp"
 #include "prost/linop/sym_gradient2d.hpp"
 
 namespace prost {
@@ -238,6 +239,36 @@ class BlockConv2D : public ProductBlock<T> {
   virtual void Product(T* res, const T* rhs, bool transpose, bool accumulate);
   conv2d::Geometry geometry_[2];           ///< the forward [0] and the adjoint [1] direction
   std::vector<T> window_[2];               ///< the window rounded to T, and flipped in both axes
+  std::vector<int32_t> words_[2];          ///< the tap tables (conv2d::Tap<T> records) as they are uploaded
+  size_t ntaps_ = 0;
+  device_vector<int32_t> d_taps_[2];
+};
+
+/// blur, then keep every s-th pixel, K = S B, without a matrix: the operator of super-resolution, and its adjoint, the fractionally
+/// strided convolution.  The window, the planes and the shape are those of BlockConv2D; stride (sy, sx), 1 .. 4 each, and phase
+/// (py, px) pick the results that are kept.  L my mx rows by L ny nx columns.  Arithmetic, tile table and table layout:
+/// prost/linop/conv2d_strided.hpp.  No describe(): the block runs on the generic paths.  Only O(taps) data is stored.
+template <typename T>
+class BlockConv2DStrided : public ProductBlock<T> {
+ public:
+  /// checks every argument (messages start with "BlockConv2DStrided: "); kernel: ky x kx, column-major; declared_rows /
+  /// declared_cols < 0: no size was declared
+  static BlockConv2DStrided<T>* Create(size_t row, size_t col, double nx, double ny, double L, const std::vector<double>& kernel, size_t ky, size_t kx,
+                                       const std::string& shape, double sy, double sx, double py, double px, double declared_rows = -1, double declared_cols = -1);
+  virtual void Initialize();
+  virtual void Release();
+  virtual T row_sum(size_t row, T alpha) const;
+  virtual T col_sum(size_t col, T alpha) const;
+  virtual void row_sums(T* out, T alpha) const;              ///< one table of class sums per call, one look-up per pixel
+  virtual void col_sums(T* out, T alpha) const;
+  virtual size_t gpu_mem_amount() const { return (words_[0].size() + words_[1].size()) * sizeof(int32_t); }
+  size_t taps() const { return ntaps_; }
+
+ protected:
+  BlockConv2DStrided(size_t row, size_t col, size_t nrows, size_t ncols) : ProductBlock<T>(row, col, nrows, ncols) {}
+  virtual void Product(T* res, const T* rhs, bool transpose, bool accumulate);
+  conv2d_strided::Geometry geometry_[2];   ///< the forward [0] and the adjoint [1] direction
+  std::vector<T> window_;                  ///< the window rounded to T
   std::vector<int32_t> words_[2];          ///< the tap tables (conv2d::Tap<T> records) as they are uploaded
   size_t ntaps_ = 0;
   device_vector<int32_t> d_taps_[2];

@@ -232,6 +232,39 @@ int prost_hip_conv2d_f32(const prost_hip_conv2d_geometry* geometry, const prost_
                          int accumulate, void* stream);
 int prost_hip_conv2d_f64(const prost_hip_conv2d_geometry* geometry, const prost_hip_conv2d_tap_f64* taps, size_t ntaps, double* res, const double* rhs,
                          int accumulate, void* stream);
+/* BlockConv2DStrided (additions; ABI version unchanged; kernels_linop_conv2d_strided.hip, arithmetic, order of operations, tile table
+ * and table layout: prost/linop/conv2d_strided.hpp): K = S B, the window applied at every pixel of `planes` column-major image planes of
+ * ny x nx (zero padding) and the results at (y sy + py, x sx + px) of the cropped convolution kept, my x mx per plane:
+ *   transpose == 0:  res(y, x) = sum_{i, j} k(i, j) rhs(y sy + py + oy - i, x sx + px + ox - j)           rhs: images, res: outputs
+ *   transpose != 0:  res(v, u) = sum_{i, j, y, x : y sy + py + oy - i = v, x sx + px + ox - j = u} k(i, j) rhs(y, x)
+ * The geometry record is a HOST pointer, read before the call returns; it describes the operator, not the direction, except for
+ * `transpose` and the class table.  taps: ntaps records in device memory (the records of prost_hip_conv2d_*), one per non-zero tap,
+ * value already rounded to T, in the order they are to be added.  Forward: j descending, inside that i descending, offset = the cell
+ * of (ky - 1 - i, kx - 1 - j) in the de-interleaved tile of the tile-table entry the header picks for (T, sy, sx, ky, kx);
+ * class_start = { 0, ntaps, .., ntaps }.  Adjoint: one sub-list per residue class c = ry sx + rx of the destination pixel,
+ * [class_start[c], class_start[c + 1]), each j ascending and inside that i ascending over i = py + oy - ry mod sy,
+ * j = px + ox - rx mod sx; class_start[sy sx ..] = ntaps.  prost::conv2d_strided::CompactTaps makes both; the offsets are trusted (a
+ * wrong one reads outside the staged tile).  accumulate != 0 stores res + value instead of value; an adjoint class without taps
+ * stores 0.  Any alignment of T is accepted.  Aliasing: res and rhs must NOT overlap, and the table overlaps neither.  No atomics: a
+ * call repeats its bits.  No allocation, copy or synchronisation.  Refused without a launch: a null pointer, a window outside
+ * 1 .. 31, a stride outside 1 .. 4, a phase outside 0 .. stride - 1, an offset outside the window, sizes below 1, a plane of 2^31
+ * elements or more, a tap count outside 1 .. ky kx, a class table that does not ascend from 0 to ntaps. */
+#define PROST_HIP_CONV2D_STRIDED_MAX_STRIDE 4
+typedef struct prost_hip_conv2d_strided_geometry {
+  int32_t ny, nx;       /* image plane */
+  int32_t my, mx;       /* decimated output plane */
+  int32_t oy, ox;       /* crop offset into the full convolution */
+  int32_t ky, kx;       /* window */
+  int32_t sy, sx;       /* stride */
+  int32_t py, px;       /* phase */
+  int32_t planes;
+  int32_t transpose;
+  int32_t class_start[PROST_HIP_CONV2D_STRIDED_MAX_STRIDE * PROST_HIP_CONV2D_STRIDED_MAX_STRIDE + 1];
+} prost_hip_conv2d_strided_geometry;
+int prost_hip_conv2d_strided_f32(const prost_hip_conv2d_strided_geometry* geometry, const prost_hip_conv2d_tap_f32* taps, size_t ntaps, float* res,
+                                 const float* rhs, int accumulate, void* stream);
+int prost_hip_conv2d_strided_f64(const prost_hip_conv2d_strided_geometry* geometry, const prost_hip_conv2d_tap_f64* taps, size_t ntaps, double* res,
+                                 const double* rhs, int accumulate, void* stream);
 /* BlockSymGradient2D (additions; ABI version unchanged; kernels_linop_sym_gradient2d.hip, arithmetic and order of operations:
  * prost/linop/sym_gradient2d.hpp): the symmetrised gradient E of a vector field on L channels of an ny x nx grid, N = nx ny, pixel
  * (y, x) at p = y + x ny.  Domain, 2 L N values: vx_c[p] at c N + p, vy_c[p] at (L + c) N + p (the range layout of gradient2d).  Range,

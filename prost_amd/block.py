@@ -156,6 +156,79 @@ def conv2d(nx, ny, L, kernel, shape="full"):
     return lambda row, col, nrows, ncols: [["conv2d", row, col, data], sz]
 
 
+CONV2D_STRIDED_MAX_STRIDE = 4
+
+
+def _pair(name, v, what):
+    """an int or a pair (y, x) of ints -> (y, x)"""
+    vs = (v, v) if isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) else v
+    try:
+        vs = tuple(vs)
+    except TypeError:
+        raise ValueError("%s: the %s %r has to be an integer or a pair (y, x)" % (name, what, v))
+    if len(vs) != 2:
+        raise ValueError("%s: the %s %r has to be an integer or a pair (y, x)" % (name, what, v))
+    for e in vs:
+        if isinstance(e, bool) or not isinstance(e, (int, float, np.integer, np.floating)) or not np.isfinite(e) or int(e) != e:
+            raise ValueError("%s: the %s %r is not an integer" % (name, what, v))
+    return int(vs[0]), int(vs[1])
+
+
+def conv2d_strided_size(nx, ny, ky, kx, stride, shape="same", phase=(0, 0)):
+    """-> (my, mx): the size of one decimated output plane, my = (cy - 1 - py) // sy + 1 with (cy, cx) the size of conv2d's output"""
+    (sy, sx), (py, px) = _pair("conv2d_strided", stride, "stride"), _pair("conv2d_strided", phase, "phase")
+    try:
+        (cy, cx), _ = conv2d_size(nx, ny, ky, kx, shape)
+    except ValueError:
+        raise ValueError("conv2d_strided: unknown shape %r (full, same or valid)" % (shape,))
+    return (cy - 1 - py) // sy + 1, (cx - 1 - px) // sx + 1
+
+
+def conv2d_strided(nx, ny, L, kernel, stride, shape="same", phase=(0, 0)):
+    """Blur, then keep every s-th pixel, K = S B, applied without a matrix: the operator of super-resolution.  Images, window and shape
+    as conv2d (L column-major planes of ny x nx, one ky x kx window of up to 31 x 31, zero padding; the shape gives the size (cy, cx)
+    and the crop offset (oy, ox) of the un-decimated convolution).  stride: s or (sy, sx), 1 .. 4 each; phase: p or (py, px) with
+    0 <= py < min(sy, cy), 0 <= px < min(sx, cx).  out(y, x) = sum_{i, j} kernel[i, j] in(y sy + py + oy - i, x sx + px + ox - j),
+    my x mx = conv2d_strided_size(..) outputs per plane: the rows (y sy + py, x sx + px) of conv2d's matrix.  The adjoint is the
+    fractionally strided ("transposed") convolution."""
+    for name, v in (("nx", nx), ("ny", ny), ("L", L)):
+        if isinstance(v, bool) or not np.isfinite(v) or int(v) != v:
+            raise ValueError("conv2d_strided: %s = %r is not an integer" % (name, v))
+        if v < 1:
+            raise ValueError("conv2d_strided: %s = %r has to be at least 1" % (name, v))
+    nx, ny, L = int(nx), int(ny), int(L)
+    kernel = np.array(kernel, dtype=np.float64, order="F", copy=True)
+    if kernel.ndim != 2 or kernel.size == 0:
+        raise ValueError("conv2d_strided: the window has to be a non-empty matrix (2-D), got shape %r" % (kernel.shape,))
+    ky, kx = kernel.shape
+    if ky > CONV2D_MAX_WINDOW or kx > CONV2D_MAX_WINDOW:
+        raise ValueError("conv2d_strided: the window is %d x %d, windows up to %d x %d are supported" % (ky, kx, CONV2D_MAX_WINDOW, CONV2D_MAX_WINDOW))
+    if not np.isfinite(kernel).all():
+        raise ValueError("conv2d_strided: the window holds a non-finite value")
+    if not kernel.any():
+        raise ValueError("conv2d_strided: the window has no non-zero tap")
+    if not isinstance(shape, str) or shape not in ("full", "same", "valid"):
+        raise ValueError("conv2d_strided: unknown shape %r (full, same or valid)" % (shape,))
+    (sy, sx), (py, px) = _pair("conv2d_strided", stride, "stride"), _pair("conv2d_strided", phase, "phase")
+    for name, s in (("sy", sy), ("sx", sx)):
+        if not 1 <= s <= CONV2D_STRIDED_MAX_STRIDE:
+            raise ValueError("conv2d_strided: the stride %s = %d has to be 1 .. %d" % (name, s, CONV2D_STRIDED_MAX_STRIDE))
+    (cy, cx), _ = conv2d_size(nx, ny, ky, kx, shape)
+    if cy < 1 or cx < 1:
+        raise ValueError("conv2d_strided: the window (%d x %d) is larger than the image (%d x %d): the valid part is empty" % (ky, kx, ny, nx))
+    for name, p, s, c in (("py", py, sy, cy), ("px", px, sx, cx)):
+        if not 0 <= p < min(s, c):
+            raise ValueError("conv2d_strided: the phase %s = %d has to be 0 .. %d (below the stride and the size of the convolution)" % (name, p, min(s, c) - 1))
+    my, mx = (cy - 1 - py) // sy + 1, (cx - 1 - px) // sx + 1
+    if nx * ny >= 2 ** 31 or my * mx >= 2 ** 31:
+        raise ValueError("conv2d_strided: a plane of %d elements; it has to stay below 2^31" % max(nx * ny, my * mx))
+    if max(nx, ny) >= 2 ** 31 - 1024 - CONV2D_MAX_WINDOW:
+        raise ValueError("conv2d_strided: a side of %d pixels; it has to stay below 2^31 - 1055" % max(nx, ny))
+    sz = [L * my * mx, L * ny * nx]
+    data = [nx, ny, L, kernel, shape, sy, sx, py, px]
+    return lambda row, col, nrows, ncols: [["conv2d_strided", row, col, data], sz]
+
+
 SYM_GRADIENT2D_MAX_SIZE = 2 ** 53          # sizes travel as doubles
 
 

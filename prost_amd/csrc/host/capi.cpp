@@ -454,6 +454,17 @@ std::map<std::string, typename Factory<T>::BlockFactory>& Factory<T>::block_reg(
                                     std::vector<double>(pm->data.begin(), pm->data.begin() + pm->rows * pm->cols), pm->rows, pm->cols, d->cells[4]->str,
                                     size.first, size.second);
     };
+    // blur and decimate without a matrix: cells { nx, ny, L, kernel (ky x kx full matrix), shape, sy, sx, py, px }; a caller that also knows
+    // the size it means the block to have appends { nrows, ncols } and gets it checked.  Every argument check is BlockConv2DStrided<T>::Create's.
+    reg["conv2d_strided"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
+      const auto size = declared_size(d, 9, "BlockConv2DStrided: the data cells are { nx, ny, L, kernel, shape, sy, sx, py, px } or { nx, ny, L, kernel, shape, sy, sx, py, px, nrows, ncols }.");
+      const prost_value* pm = d->cells[3];
+      if (!pm || pm->kind != PROST_VALUE_MATRIX) throw Exception("BlockConv2DStrided: the window has to be a full matrix of type single or double.");
+      if (!d->cells[4] || d->cells[4]->kind != PROST_VALUE_STRING) throw Exception("BlockConv2DStrided: the shape has to be a string (full, same or valid).");
+      return BlockConv2DStrided<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2),
+                                           std::vector<double>(pm->data.begin(), pm->data.begin() + pm->rows * pm->cols), pm->rows, pm->cols, d->cells[4]->str,
+                                           GetScalarFromCell(d, 5), GetScalarFromCell(d, 6), GetScalarFromCell(d, 7), GetScalarFromCell(d, 8), size.first, size.second);
+    };
     // the symmetrised gradient of TGV^2 without a matrix: cells { nx, ny, L, w }; a caller that also knows the size it means the block to
     // have appends { nrows, ncols } and gets it checked.  Every argument check is BlockSymGradient2D<T>::Create's.
     reg["sym_gradient2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {

@@ -568,6 +568,102 @@ void BlockConv2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
 template class BlockConv2D<float>;
 template class BlockConv2D<double>;
 
+// ---- blur and decimate: strided 2-D convolution without a matrix ----
+template <typename T>
+BlockConv2DStrided<T>* BlockConv2DStrided<T>::Create(size_t row, size_t col, double nx, double ny, double L, const std::vector<double>& kernel, size_t ky, size_t kx,
+                                                     const std::string& shape, double sy, double sx, double py, double px, double declared_rows,
+                                                     double declared_cols) {
+  namespace c2s = conv2d_strided;
+  std::stringstream ss;
+  ss << "BlockConv2DStrided: ";
+  const double kMaxPlane = 2147483648.0, kMaxSide = kMaxPlane - 1024 - conv2d::kMaxWindow;      // 2^31; sides leave room for a tile's halo
+  for (const auto& v : {std::make_pair("nx", nx), std::make_pair("ny", ny), std::make_pair("L", L)})
+    if (!(v.second >= 1) || v.second != std::floor(v.second) || v.second >= kMaxPlane) {
+      ss << v.first << " = " << v.second << " has to be a positive integer below 2^31."; throw Exception(ss.str());
+    }
+  if (ky == 0 || kx == 0 || kernel.size() != ky * kx) { ss << "the window is empty."; throw Exception(ss.str()); }
+  if (ky > (size_t)conv2d::kMaxWindow || kx > (size_t)conv2d::kMaxWindow) {
+    ss << "the window is " << ky << " x " << kx << ", windows up to " << conv2d::kMaxWindow << " x " << conv2d::kMaxWindow << " are supported."; throw Exception(ss.str());
+  }
+  for (double v : kernel)
+    if (!std::isfinite(v)) { ss << "the window holds a non-finite value."; throw Exception(ss.str()); }
+  int which = -1;
+  if (shape == "full") which = conv2d::kFull;
+  else if (shape == "same") which = conv2d::kSame;
+  else if (shape == "valid") which = conv2d::kValid;
+  else { ss << "unknown shape '" << shape << "' (full, same or valid)."; throw Exception(ss.str()); }
+  for (const auto& v : {std::make_pair("sy", sy), std::make_pair("sx", sx)})
+    if (!(v.second >= 1) || v.second != std::floor(v.second) || v.second > c2s::kMaxStride) {
+      ss << "the stride " << v.first << " = " << v.second << " has to be an integer from 1 to " << c2s::kMaxStride << "."; throw Exception(ss.str());
+    }
+  long cy = 0, cx = 0, oy = 0, ox = 0;
+  if (!conv2d::OutputSize(which, (long)ny, (long)nx, (long)ky, (long)kx, cy, cx, oy, ox)) {
+    ss << "the window (" << ky << " x " << kx << ") is larger than the image (" << ny << " x " << nx << "): the valid part is empty."; throw Exception(ss.str());
+  }
+  for (const auto& v : {std::make_pair(std::make_pair("py", py), std::min((long)sy, cy)), std::make_pair(std::make_pair("px", px), std::min((long)sx, cx))})
+    if (!(v.first.second >= 0) || v.first.second != std::floor(v.first.second) || v.first.second >= (double)v.second) {
+      ss << "the phase " << v.first.first << " = " << v.first.second << " has to be an integer from 0 to " << v.second - 1 << " (below the stride and the size of the convolution).";
+      throw Exception(ss.str());
+    }
+  long my = 0, mx = 0;
+  c2s::OutputSize(which, (long)ny, (long)nx, (long)ky, (long)kx, (long)sy, (long)sx, (long)py, (long)px, my, mx, oy, ox);
+  if (nx * ny >= kMaxPlane || (double)my * (double)mx >= kMaxPlane) { ss << "a plane of " << std::max(nx * ny, (double)my * (double)mx) << " elements; it has to stay below 2^31."; throw Exception(ss.str()); }
+  if (std::max(nx, ny) >= kMaxSide) { ss << "a side of " << std::max(nx, ny) << " pixels; it has to stay below 2^31 - 1055."; throw Exception(ss.str()); }
+  const double rows = L * (double)my * (double)mx, cols = L * ny * nx;
+  if ((declared_rows >= 0 || declared_cols >= 0) && (declared_rows != rows || declared_cols != cols)) {
+    ss << "the declared size " << declared_rows << " x " << declared_cols << " is not L my mx x L ny nx = " << rows << " x " << cols << "."; throw Exception(ss.str());
+  }
+  std::unique_ptr<BlockConv2DStrided<T>> b(new BlockConv2DStrided<T>(row, col, (size_t)rows, (size_t)cols));
+  b->window_ = c2s::Window<T>(kernel.data(), (long)ky, (long)kx);
+  const int tile = c2s::PickTile(sizeof(T), (int)sy, (int)sx, (int)ky, (int)kx);
+  if (tile < 0) { ss << "no tile of the table fits the window and the stride."; throw Exception(ss.str()); }
+  for (int dir = 0; dir < 2; dir++) {
+    b->geometry_[dir] = c2s::MakeGeometry(which, (long)ny, (long)nx, (long)ky, (long)kx, (long)sy, (long)sx, (long)py, (long)px, (long)L, dir == 1);
+    const std::vector<conv2d::Tap<T>> taps = c2s::CompactTaps<T>(b->geometry_[dir], b->window_, tile);
+    b->words_[dir].assign(taps.size() * (sizeof(conv2d::Tap<T>) / sizeof(int32_t)), 0);
+    for (size_t t = 0; t < taps.size(); t++) {     // field by field: the padding of the fp64 record stays zero
+      int32_t* w = b->words_[dir].data() + t * (sizeof(conv2d::Tap<T>) / sizeof(int32_t));
+      std::memcpy(w, &taps[t].offset, sizeof(int32_t));
+      std::memcpy(reinterpret_cast<char*>(w) + offsetof(conv2d::Tap<T>, value), &taps[t].value, sizeof(T));
+    }
+    b->ntaps_ = taps.size();
+  }
+  if (b->ntaps_ == 0) { ss << "the window has no non-zero tap" << (std::is_same<T, float>::value ? " in single precision." : "."); throw Exception(ss.str()); }
+  return b.release();
+}
+template <typename T>
+void BlockConv2DStrided<T>::Initialize() { for (int dir = 0; dir < 2; dir++) d_taps_[dir] = words_[dir]; }
+template <typename T>
+void BlockConv2DStrided<T>::Release() { for (int dir = 0; dir < 2; dir++) d_taps_[dir].clear(); }
+template <typename T>
+T BlockConv2DStrided<T>::row_sum(size_t row, T alpha) const {
+  const conv2d_strided::Geometry& g = geometry_[0];
+  const size_t p = row % ((size_t)g.my * (size_t)g.mx);
+  return (T)conv2d_strided::SumAt<T>(g, window_, (double)alpha, false, (int)(p % (size_t)g.my), (int)(p / (size_t)g.my));
+}
+template <typename T>
+T BlockConv2DStrided<T>::col_sum(size_t col, T alpha) const {
+  const conv2d_strided::Geometry& g = geometry_[0];
+  const size_t p = col % ((size_t)g.ny * (size_t)g.nx);
+  return (T)conv2d_strided::SumAt<T>(g, window_, (double)alpha, true, (int)(p % (size_t)g.ny), (int)(p / (size_t)g.ny));
+}
+template <typename T>
+void BlockConv2DStrided<T>::row_sums(T* out, T alpha) const { conv2d_strided::Sums<T>(geometry_[0], window_, (double)alpha, false, out); }
+template <typename T>
+void BlockConv2DStrided<T>::col_sums(T* out, T alpha) const { conv2d_strided::Sums<T>(geometry_[0], window_, (double)alpha, true, out); }
+template <typename T>
+void BlockConv2DStrided<T>::Product(T* r, const T* x, bool transpose, bool acc) {
+  const int dir = transpose ? 1 : 0;
+  if (d_taps_[dir].size() != words_[dir].size()) throw Exception("BlockConv2DStrided used before Initialize().");
+  typedef typename std::conditional<std::is_same<T, float>::value, prost_hip_conv2d_tap_f32, prost_hip_conv2d_tap_f64>::type Record;
+  static_assert(sizeof(Record) == sizeof(conv2d::Tap<T>) && sizeof(prost_hip_conv2d_strided_geometry) == sizeof(conv2d_strided::Geometry), "records of prost_hip.h");
+  CheckHip(Api<T>::conv2d_strided(reinterpret_cast<const prost_hip_conv2d_strided_geometry*>(&geometry_[dir]), reinterpret_cast<const Record*>(d_taps_[dir].data()),
+                                  ntaps_, r, x, acc ? 1 : 0, CurrentStream()),
+           "conv2d_strided");
+}
+template class BlockConv2DStrided<float>;
+template class BlockConv2DStrided<double>;
+
 // ---- the symmetrised gradient of TGV^2, without a matrix ----
 template <typename T>
 BlockSymGradient2D<T>* BlockSymGradient2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, double w, double declared_rows, double declared_cols) {
