@@ -9,6 +9,7 @@
 #include <functional>
 
 #include "prost/backend/backend.hpp"
+#include "prost/backend/pdhg_pair_plan.hpp"
 #include "prost_hip.h"
 
 namespace prost {
@@ -45,7 +46,8 @@ class BackendPDHG : public Backend<T> {
                                ///< contract multiply-adds (what nvcc's default does to the reference's kernels) and divide through fp32 reciprocal
                                ///< instructions; where a K-iterations-per-launch kernel exists for the problem (fp32 gray-value ROF / TV-L1 shapes) up
                                ///< to 4 iterations run per launch.  Iterates within a stated tolerance of the exact ones (tests/test_gpu_fmad.py).
-    int group_max;             ///< MI355X addition (round 6): iterations per launch of the K-iteration kernel; 0 = the class's default, 1 = never (pairs)
+    int group_max;             ///< MI355X addition (round 6): iterations per launch of the K-iteration kernel; 0 = the class's default (tolerance class: groups
+                               ///< of up to 4; exact class: pairs, with one launch of four in place of two plain pairs on large images), 1 = never (pairs)
     Options() : tau0(1), sigma0(1), residual_iter(1), scale_steps_operator(true), alg2_gamma(0), arg_alpha0(0.5),
                 arg_nu(0.95), arg_delta(1.5), arb_delta(1.05), arb_tau(0.8), stepsize_variant(kPDHGStepsResidualBoyd),
                 allow_fused(true), allow_single_kernel(true), allow_pair_kernel(true), allow_arg_fusion(true), allow_op_fusion(0), residual_sums_in_prox(1), allow_speculation(true),
@@ -101,6 +103,12 @@ class BackendPDHG : public Backend<T> {
     return fused_ && (desc_pair_.arith == PROST_HIP_ARITH_FMAD || desc_.arith == PROST_HIP_ARITH_FMAD) ? PROST_HIP_ARITH_FMAD : PROST_HIP_ARITH_EXACT;
   }
   int group_max() const { return group_max_; }
+  /// Exact class: two consecutive plain pairs run as ONE launch of four iterations (fours_; pdhg_pair_plan.hpp, kPairPlanFours).
+  /// Smallest image (pixels) the launch of four replaces two plain pairs at: the smallest size it was measured ahead at.  One launch
+  /// of four against the two plain pair launches it replaces, per iteration: 1024^2 8.2 against 9.8 us, 2048^2 16.9 / 18.7, 3072^2
+  /// 28.4 / 32.1, 4096^2 44.5 / 49.9, 8192^2 158 / 264 (docs/rounds/r22.md section 4); smaller images were not measured and keep the
+  /// pairs.  PROST_PDHG_FOURS_MIN_PIXELS overrides it (tests).
+  static constexpr size_t kFoursMinPixels = (size_t)1024 * 1024;
   /// the residual-driven rule runs on the device for this problem / option set (batches of iterations, one host wait each)
   bool device_rules() const { return dev_rules_ || dev_rules_generic_; }
   /// batches of iterations that ran with the step-size rule and the stopping test on the device
@@ -146,6 +154,7 @@ class BackendPDHG : public Backend<T> {
   bool single_pw_ = false;
   MultiKind multi_ = kMultiNone;
   int group_max_ = 0;
+  bool fours_ = false;                     // kMultiPair only: the pair plan with launches of four
   bool gray_multi() const { return multi_ == kMultiPair || multi_ == kMultiGroup; }
   bool TryFused();
   bool DescribeProxG(ProxDesc& out);         // prox_g as one elem_operation:1d over the whole primal variable (pieces merged)
@@ -169,7 +178,7 @@ class BackendPDHG : public Backend<T> {
   // ---- the launch plan ------------------------------------------------------------------------------------------------------------------
   /// what runs next: `count` iterations in one launch; `residuals`: the last of them is a residual iteration (its sums are formed in
   /// the kernel); `store_mid`: a pair that also stores the iterate in between
-  struct Launch { int count; bool residuals, store_mid; };
+  typedef PdhgLaunch Launch;
   Launch NextLaunch(size_t k, int room) const;
   int GroupSize(size_t k, int budget, bool& residuals) const;
   /// the step sizes a launch ran with: (tau, sigma, theta) of iteration i of the launch, and at [count] the values after it

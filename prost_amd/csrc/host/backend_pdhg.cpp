@@ -272,17 +272,24 @@ void BackendPDHG<T>::Initialize() {
   // at the 2048 x 2048 x 64 size until somebody reads the solution
   // tolerance-class arithmetic (Options::arithmetic): where the K-iterations-per-launch kernel takes the description, groups of up to
   // kGroupMax iterations replace the pairs; elsewhere the solve stays exact (exact results satisfy every tolerance)
-  group_max_ = 0; last_ = LaunchSteps();
+  group_max_ = 0; fours_ = false; last_ = LaunchSteps();
   desc_.arith = desc_pair_.arith = PROST_HIP_ARITH_EXACT;
   if (pair_kernel && owned_x1_ == 0 && opts_.group_max != 1) {
     prost_hip_fused_desc probe = desc_pair_;
     probe.arith = opts_.arithmetic == PROST_HIP_ARITH_FMAD ? PROST_HIP_ARITH_FMAD : PROST_HIP_ARITH_EXACT;
     const int kmax = prost_hip_fused_iterationk_max(&probe, dtype_id<T>());
     // tolerance class: groups of up to kGroupMax.  Exact class: the K-iteration kernel with the exact forms equals the pair kernel and the
-    // oracle bit for bit, but its launches are bound by instruction issue (~48 us per iteration whatever K: 4096^2, K = 2 / 3 / 4: 0.106 /
-    // 0.145 / 0.204 ms per launch), so groups buy nothing there: pairs stay the default, Options::group_max > 1 asks for groups (tests)
+    // oracle bit for bit.  Its single-wave instances hold all 2K stages in one wavefront (4096^2, K = 2 / 3 / 4: 0.106 / 0.145 / 0.204 ms
+    // per launch, no better than pairs); with one level per wavefront a launch of four takes 0.178 ms, a launch of three 0.154 ms
+    // (docs/rounds/r22.md).  So pairs stay the default plan, and on large images a launch of four replaces two consecutive PLAIN pairs
+    // (fours_, pdhg_pair_plan.hpp); Options::group_max > 1 asks for the group plan explicitly (tests).
     const int want = opts_.group_max > 1 ? opts_.group_max : (probe.arith == PROST_HIP_ARITH_FMAD ? kGroupMax : 1);
     if (kmax >= 2 && want >= 2) { group_max_ = std::min(std::min(kmax, kGroupMax), want); desc_pair_.arith = probe.arith; }
+    if (group_max_ == 0 && opts_.group_max == 0 && probe.arith == PROST_HIP_ARITH_EXACT && kmax >= 4) {
+      const char* e = getenv("PROST_PDHG_FOURS_MIN_PIXELS");
+      const size_t min_pixels = e && e[0] ? (size_t)strtoull(e, nullptr, 10) : kFoursMinPixels;
+      fours_ = (size_t)desc_pair_.nx * (size_t)desc_pair_.ny >= min_pixels;
+    }
   }
   // gradient3d volumes / 2-4 channels: the pair kernels have tolerance-class instances of their own (two iterations per launch as before)
   if (opts_.arithmetic == PROST_HIP_ARITH_FMAD && pair3d) {
@@ -629,22 +636,23 @@ int BackendPDHG<T>::GroupSize(size_t k, int budget, bool& residuals) const {
 /// k alone then, so that at an even residual_iter their residual iterations are always the second of a pair.
 template <typename T>
 typename BackendPDHG<T>::Launch BackendPDHG<T>::NextLaunch(size_t k, int room) const {
-  const Launch one{1, is_residual_iteration(k), false};
+  const Launch one{1, is_residual_iteration(k), false, false};
   if (multi_ == kMultiNone || room < 2 || k < 2 || one.residuals) return one;
   if (multi_ == kMultiGroup) {
     bool residuals = false;
     const int g = GroupSize(k, room, residuals);
-    return Launch{g, residuals, false};
+    return Launch{g, residuals, false, true};
   }
-  const bool observed_mid = is_residual_iteration(k + 2);
-  if (observed_mid && multi_ != kMultiPair) return one;
-  return Launch{2, is_residual_iteration(k + 1), observed_mid};
+  // gray values, exact class: pairs, and where two plain pairs would follow one another a launch of four (fours_)
+  if (multi_ == kMultiPair) return pdhg_pair_plan(k, room, (size_t)opts_.residual_iter, fours_ ? kPairPlanFours : kPairPlanPairs);
+  if (is_residual_iteration(k + 2)) return one;
+  return Launch{2, is_residual_iteration(k + 1), false, false};
 }
 
 /// the step sizes of iterations k .. k+count-1 (alg2 changes them every iteration, :483-488): tau_ / sigma_ / theta_ end as those of the last one
 template <typename T>
 void BackendPDHG<T>::StepsOfLaunch(LaunchSteps& steps, int count) {
-  steps.count = count; steps.group = multi_ == kMultiGroup;
+  steps.count = count; steps.group = multi_ == kMultiGroup || count > 2;        // (count > 2: a launch of four of the pair plan)
   for (int i = 0; i < count; i++) {
     if (i > 0 && opts_.stepsize_variant == kPDHGStepsAlg2) UpdateAlg2();
     steps.tau[i] = tau_; steps.sigma[i] = sigma_; steps.theta[i] = theta_;
@@ -664,10 +672,11 @@ void BackendPDHG<T>::LaunchMulti(int count, bool residuals, const LaunchSteps& s
   const unsigned long long it = (unsigned long long)iteration_;        // the index of the launch's last iteration
   double* sums = residuals ? res_target() : nullptr;
   void* ws = residuals ? workspace_ : nullptr;
-  const int kind = rebuild ? kUntimed : multi_ == kMultiGroup ? (residuals ? kKernelGroup2Res : kKernelGroup2) + (count - 2)
+  const bool group = multi_ == kMultiGroup || count > 2;      // the K-iteration kernel: the group plan, or a launch of four (three: its rebuild) of the pair plan
+  const int kind = rebuild ? kUntimed : group ? (residuals ? kKernelGroup2Res : kKernelGroup2) + (count - 2)
                    : x_mid ? (residuals ? kKernelPairMidRes : kKernelPairMid) : (residuals ? kKernelPairRes : kKernelPair);
   TimedLaunch(kind, [&] {
-    switch (multi_) {
+    switch (group ? kMultiGroup : multi_) {
       case kMultiPair:
         if (rec) CheckHip(Api<T>::fused_iteration2_rec(&desc_pair_, x_out, y_out, x, y, x_mid, y_mid, rule_rec_, 0, sums, ws, rule, it, rule_mirror_dev_, s), "fused_iteration2_rec");
         else CheckHip(Api<T>::fused_iteration2(&desc_pair_, x_out, y_out, x, y, x_mid, y_mid, tau, sigma, theta, 0, sums, ws, s), "fused_iteration2");
