@@ -6,6 +6,7 @@
 #include "prost/linop/block.hpp"
 #include "prost/linop/conv2d.hpp"
 #include "prost/linop/conv2d_strided.hpp"
+#include "prost/linop/radon2d.hpp"
 #include "prost/linop/sym_gradient2d.hpp"
 
 namespace prost {
@@ -272,6 +273,34 @@ class BlockConv2DStrided : public ProductBlock<T> {
   std::vector<int32_t> words_[2];          ///< the tap tables (conv2d::Tap<T> records) as they are uploaded
   size_t ntaps_ = 0;
   device_vector<int32_t> d_taps_[2];
+};
+
+/// the parallel-beam projector of tomography (Joseph's method) and its exact transpose, without a matrix: L column-major planes of
+/// ny x nx onto L sinograms of na angles x ndet bins.  L na ndet rows by L ny nx columns.  Geometry, per-angle table, arithmetic and the
+/// candidate window of the adjoint: prost/linop/radon2d.hpp.  No describe(): the block runs on the generic paths.  Only the table,
+/// five numbers per angle, is stored.
+template <typename T>
+class BlockRadon2D : public ProductBlock<T> {
+ public:
+  /// checks every argument (messages start with "BlockRadon2D: "); ndet < 0 (or NaN): the default detector length; declared_rows /
+  /// declared_cols < 0: no size was declared
+  static BlockRadon2D<T>* Create(size_t row, size_t col, double nx, double ny, double L, const std::vector<double>& angles, double ndet, double spacing, double shift,
+                                 double declared_rows = -1, double declared_cols = -1);
+  virtual void Initialize();
+  virtual void Release();
+  virtual T row_sum(size_t row, T alpha) const;
+  virtual T col_sum(size_t col, T alpha) const;
+  virtual void row_sums(T* out, T alpha) const;              ///< one plane enumerated once on several host threads, then repeated for every plane
+  virtual void col_sums(T* out, T alpha) const;
+  virtual size_t gpu_mem_amount() const { return table_.size() * sizeof(T); }
+  const radon2d::Geometry& geometry() const { return geometry_; }
+
+ protected:
+  BlockRadon2D(size_t row, size_t col, size_t nrows, size_t ncols) : ProductBlock<T>(row, col, nrows, ncols) {}
+  virtual void Product(T* res, const T* rhs, bool transpose, bool accumulate);
+  radon2d::Geometry geometry_;
+  std::vector<T> table_;                   ///< the per-angle table as it is uploaded
+  device_vector<T> d_table_;
 };
 
 /// the symmetrised gradient of a vector field on L channels of an ny x nx grid, without a matrix: the second-order operator of TGV^2

@@ -265,6 +265,29 @@ int prost_hip_conv2d_strided_f32(const prost_hip_conv2d_strided_geometry* geomet
                                  const float* rhs, int accumulate, void* stream);
 int prost_hip_conv2d_strided_f64(const prost_hip_conv2d_strided_geometry* geometry, const prost_hip_conv2d_tap_f64* taps, size_t ntaps, double* res,
                                  const double* rhs, int accumulate, void* stream);
+/* BlockRadon2D (additions; ABI version unchanged; kernels_linop_radon2d.hip, arithmetic, order of operations, table layout and the
+ * candidate window of the adjoint: prost/linop/radon2d.hpp): the parallel-beam projector K (Joseph's method) of `planes` column-major
+ * image planes of ny x nx onto `planes` sinograms of na angles x ndet bins (bin d of angle a at d + a ndet), and its exact transpose:
+ *   transpose == 0:  res(a, d) = sum over the driving lines t of (c w0) rhs(t, i0) + (c w1) rhs(t, i0 + 1)       rhs: images
+ *   transpose != 0:  res(t, i) = sum over angles and candidate bins of the same entries times rhs(a, d)          rhs: sinograms
+ * The geometry record is a HOST pointer, read before the call returns.  table: na rows of PROST_HIP_RADON2D_TABLE_WIDTH values of T in
+ * device memory, { q, p, r, c, axis } per angle, already rounded to T (prost::radon2d::MakeTable makes it); the values are trusted
+ * (any finite table gives in-bounds accesses).  m is the margin of the adjoint's candidate window, ceil(1 / spacing).
+ * accumulate != 0 stores res + value instead of value; a ray that misses the image and a pixel no ray samples store 0.  Any alignment
+ * of T is accepted.  Aliasing: res and rhs must NOT overlap, and the table overlaps neither.  No atomics: a call repeats its bits.  No
+ * allocation, copy or synchronisation.  Refused without a launch: a null pointer, nx or ny outside 1 .. 8192, na outside 1 .. 4096,
+ * ndet or planes below 1, ndet above 2^31 - 1025, m outside 1 .. 2, a sinogram of 2^31 elements or more. */
+#define PROST_HIP_RADON2D_TABLE_WIDTH 5
+typedef struct prost_hip_radon2d_geometry {
+  int32_t ny, nx;       /* image plane */
+  int32_t ndet, na;     /* bins per angle, angles */
+  int32_t planes;
+  int32_t m;            /* margin of the candidate window */
+  int32_t transpose;
+  int32_t reserved;     /* 0 */
+} prost_hip_radon2d_geometry;
+int prost_hip_radon2d_f32(const prost_hip_radon2d_geometry* geometry, const float* table, float* res, const float* rhs, int accumulate, void* stream);
+int prost_hip_radon2d_f64(const prost_hip_radon2d_geometry* geometry, const double* table, double* res, const double* rhs, int accumulate, void* stream);
 /* BlockSymGradient2D (additions; ABI version unchanged; kernels_linop_sym_gradient2d.hip, arithmetic and order of operations:
  * prost/linop/sym_gradient2d.hpp): the symmetrised gradient E of a vector field on L channels of an ny x nx grid, N = nx ny, pixel
  * (y, x) at p = y + x ny.  Domain, 2 L N values: vx_c[p] at c N + p, vy_c[p] at (L + c) N + p (the range layout of gradient2d).  Range,

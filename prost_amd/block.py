@@ -229,6 +229,66 @@ def conv2d_strided(nx, ny, L, kernel, stride, shape="same", phase=(0, 0)):
     return lambda row, col, nrows, ncols: [["conv2d_strided", row, col, data], sz]
 
 
+RADON2D_MAX_SIDE = 8192
+RADON2D_MAX_ANGLES = 4096
+
+
+def _radon2d_number(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError("radon2d: %s = %r is not a number" % (name, v))
+    return float(v)
+
+
+def radon2d_ndet(nx, ny, spacing=1.0):
+    """the default detector length of radon2d: 2 ceil(hypot(nx, ny) / (2 spacing)) + 1 bins see every pixel at every angle"""
+    return 2 * int(math.ceil(math.hypot(nx, ny) / (2.0 * spacing))) + 1
+
+
+def radon2d(nx, ny, L, angles, ndet=None, spacing=1.0, shift=0.0):
+    """The parallel-beam projector of tomography (Joseph's method), applied without a matrix, and its exact transpose.  Domain: L
+    column-major planes of ny x nx, element (y, x, c) at y + x ny + c nx ny.  Range: L sinograms, bin d of angle a of plane c at
+    d + a ndet + c ndet na.  Pixel centres sit at X = x - (nx - 1) / 2, Y = y - (ny - 1) / 2 (pixel size 1); a point projects to
+    s = X cos(theta) + Y sin(theta), and bin d sits at s_d = (d - (ndet - 1) / 2) spacing + shift.  angles: radians, up to 4096;
+    ndet: None for radon2d_ndet(nx, ny, spacing); 0.5 <= spacing <= 8.  Per angle the ray is marched over the rows if
+    |cos| >= |sin| and over the columns otherwise, and interpolated linearly along the other axis; a matrix entry is the
+    interpolation weight times 1 / max(|cos|, |sin|).  Only five numbers per angle are stored."""
+    for name, v, top in (("nx", nx, RADON2D_MAX_SIDE), ("ny", ny, RADON2D_MAX_SIDE), ("L", L, None), ("ndet", ndet, None)):
+        if name == "ndet" and v is None:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or int(v) != v:
+            raise ValueError("radon2d: %s = %r is not an integer" % (name, v))
+        if v < 1:
+            raise ValueError("radon2d: %s = %r has to be at least 1" % (name, v))
+        if top is not None and v > top:
+            raise ValueError("radon2d: %s = %r has to be at most %d" % (name, v, top))
+    nx, ny, L = int(nx), int(ny), int(L)
+    try:
+        angles = np.array(angles, dtype=np.float64, copy=True)
+    except (TypeError, ValueError):
+        raise ValueError("radon2d: the angles have to be a vector of numbers")
+    if angles.ndim == 0:
+        angles = angles.reshape(1)
+    if angles.ndim != 1 or angles.size == 0:
+        raise ValueError("radon2d: the angles have to be a non-empty vector, got shape %r" % (angles.shape,))
+    if angles.size > RADON2D_MAX_ANGLES:
+        raise ValueError("radon2d: %d angles, up to %d are supported" % (angles.size, RADON2D_MAX_ANGLES))
+    if not np.isfinite(angles).all():
+        raise ValueError("radon2d: the angles hold a non-finite value")
+    spacing, shift = _radon2d_number("spacing", spacing), _radon2d_number("shift", shift)
+    if not 0.5 <= spacing <= 8:
+        raise ValueError("radon2d: spacing = %r has to be from 0.5 to 8" % (spacing,))
+    if not np.isfinite(shift):
+        raise ValueError("radon2d: shift = %r has to be finite" % (shift,))
+    ndet = radon2d_ndet(nx, ny, spacing) if ndet is None else int(ndet)
+    if ndet > 2 ** 31 - 1025:
+        raise ValueError("radon2d: ndet = %d has to be below 2^31 - 1024" % ndet)
+    if ndet * angles.size >= 2 ** 31:
+        raise ValueError("radon2d: a sinogram of %d elements; it has to stay below 2^31" % (ndet * angles.size))
+    sz = [L * angles.size * ndet, L * ny * nx]
+    data = [nx, ny, L, angles, ndet, spacing, shift]
+    return lambda row, col, nrows, ncols: [["radon2d", row, col, data], sz]
+
+
 SYM_GRADIENT2D_MAX_SIZE = 2 ** 53          # sizes travel as doubles
 
 

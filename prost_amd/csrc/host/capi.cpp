@@ -465,6 +465,16 @@ std::map<std::string, typename Factory<T>::BlockFactory>& Factory<T>::block_reg(
                                            std::vector<double>(pm->data.begin(), pm->data.begin() + pm->rows * pm->cols), pm->rows, pm->cols, d->cells[4]->str,
                                            GetScalarFromCell(d, 5), GetScalarFromCell(d, 6), GetScalarFromCell(d, 7), GetScalarFromCell(d, 8), size.first, size.second);
     };
+    // the parallel-beam projector without a matrix: cells { nx, ny, L, angles (full vector), ndet, spacing, shift }; a caller that also knows
+    // the size it means the block to have appends { nrows, ncols } and gets it checked.  Every argument check is BlockRadon2D<T>::Create's.
+    reg["radon2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
+      const auto size = declared_size(d, 7, "BlockRadon2D: the data cells are { nx, ny, L, angles, ndet, spacing, shift } or { nx, ny, L, angles, ndet, spacing, shift, nrows, ncols }.");
+      const prost_value* pa = d->cells[3];
+      if (!pa || pa->kind != PROST_VALUE_MATRIX) throw Exception("BlockRadon2D: the angles have to be a full vector of type single or double.");
+      return BlockRadon2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2),
+                                     std::vector<double>(pa->data.begin(), pa->data.begin() + pa->rows * pa->cols), GetScalarFromCell(d, 4), GetScalarFromCell(d, 5),
+                                     GetScalarFromCell(d, 6), size.first, size.second);
+    };
     // the symmetrised gradient of TGV^2 without a matrix: cells { nx, ny, L, w }; a caller that also knows the size it means the block to
     // have appends { nrows, ncols } and gets it checked.  Every argument check is BlockSymGradient2D<T>::Create's.
     reg["sym_gradient2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {

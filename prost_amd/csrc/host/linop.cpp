@@ -6,6 +6,7 @@
 #include <cstring>
 #include <mutex>
 #include <sstream>
+#include <thread>
 #include <unordered_map>
 
 #include "hipapi.hpp"
@@ -663,6 +664,101 @@ void BlockConv2DStrided<T>::Product(T* r, const T* x, bool transpose, bool acc) 
 }
 template class BlockConv2DStrided<float>;
 template class BlockConv2DStrided<double>;
+
+// ---- the parallel-beam projector of tomography, without a matrix ----
+template <typename T>
+BlockRadon2D<T>* BlockRadon2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, const std::vector<double>& angles, double ndet, double spacing, double shift,
+                                         double declared_rows, double declared_cols) {
+  namespace r2d = radon2d;
+  std::stringstream ss;
+  ss << "BlockRadon2D: ";
+  const double kMaxPlane = 2147483648.0;      // 2^31
+  for (const auto& v : {std::make_pair("nx", nx), std::make_pair("ny", ny)})
+    if (!(v.second >= 1) || v.second != std::floor(v.second) || v.second > r2d::kMaxSide) {
+      ss << v.first << " = " << v.second << " has to be an integer from 1 to " << r2d::kMaxSide << "."; throw Exception(ss.str());
+    }
+  if (!(L >= 1) || L != std::floor(L) || L >= kMaxPlane) { ss << "L = " << L << " has to be a positive integer below 2^31."; throw Exception(ss.str()); }
+  if (angles.empty()) { ss << "the angles are empty."; throw Exception(ss.str()); }
+  if (angles.size() > (size_t)r2d::kMaxAngles) { ss << angles.size() << " angles, up to " << r2d::kMaxAngles << " are supported."; throw Exception(ss.str()); }
+  for (double v : angles)
+    if (!std::isfinite(v)) { ss << "the angles hold a non-finite value."; throw Exception(ss.str()); }
+  if (!(spacing >= 0.5 && spacing <= 8)) { ss << "spacing = " << spacing << " has to be from 0.5 to 8."; throw Exception(ss.str()); }
+  if (!std::isfinite(shift)) { ss << "shift = " << shift << " has to be finite."; throw Exception(ss.str()); }
+  if (!(ndet >= 1) || ndet != std::floor(ndet) || ndet > (double)r2d::kMaxBins) { ss << "ndet = " << ndet << " has to be a positive integer below 2^31 - 1024."; throw Exception(ss.str()); }
+  const double na = (double)angles.size();
+  if (ndet * na >= kMaxPlane) { ss << "a sinogram of " << ndet * na << " elements; it has to stay below 2^31."; throw Exception(ss.str()); }
+  const double rows = L * na * ndet, cols = L * ny * nx;
+  if ((declared_rows >= 0 || declared_cols >= 0) && (declared_rows != rows || declared_cols != cols)) {
+    ss << "the declared size " << declared_rows << " x " << declared_cols << " is not L na ndet x L ny nx = " << rows << " x " << cols << "."; throw Exception(ss.str());
+  }
+  std::unique_ptr<BlockRadon2D<T>> b(new BlockRadon2D<T>(row, col, (size_t)rows, (size_t)cols));
+  b->geometry_ = r2d::MakeGeometry((long)ny, (long)nx, (long)L, (long)ndet, (long)angles.size(), spacing, false);
+  b->table_ = r2d::MakeTable<T>((long)ny, (long)nx, (long)ndet, spacing, shift, angles);
+  for (T v : b->table_)
+    if (!std::isfinite(v)) { ss << "the table of the angles is not finite" << (std::is_same<T, float>::value ? " in single precision." : "."); throw Exception(ss.str()); }
+  return b.release();
+}
+template <typename T>
+void BlockRadon2D<T>::Initialize() { d_table_ = table_; }
+template <typename T>
+void BlockRadon2D<T>::Release() { d_table_.clear(); }
+template <typename T>
+T BlockRadon2D<T>::row_sum(size_t row, T alpha) const {
+  const radon2d::Geometry& g = geometry_;
+  const size_t p = row % ((size_t)g.ndet * (size_t)g.na);
+  return (T)radon2d::RowSum<T>(table_.data(), g, (double)alpha, (int)(p / (size_t)g.ndet), (int)(p % (size_t)g.ndet));
+}
+template <typename T>
+T BlockRadon2D<T>::col_sum(size_t col, T alpha) const {
+  const radon2d::Geometry& g = geometry_;
+  const size_t p = col % ((size_t)g.ny * (size_t)g.nx);
+  return (T)radon2d::ColSum<T>(table_.data(), g, (double)alpha, (int)(p % (size_t)g.ny), (int)(p / (size_t)g.ny));
+}
+/// fn(i) -> the sum of element i of one plane, for i = 0 .. n - 1 on several host threads (`work` steps each); out[i + c n] += it for every plane c
+template <typename T, class F>
+static void radon2d_plane_sums(T* out, size_t n, size_t planes, size_t work, F fn) {
+  std::vector<T> one(n);
+  const size_t parts = std::min(n, ParallelChunks(n * std::max<size_t>(work, 1)));
+  std::vector<std::thread> th;
+  std::exception_ptr err = nullptr;
+  std::mutex mu;
+  auto run = [&](size_t k) {
+    try { for (size_t i = n * k / parts; i < n * (k + 1) / parts; i++) one[i] = (T)fn(i); }
+    catch (...) { std::lock_guard<std::mutex> lock(mu); err = std::current_exception(); }
+  };
+  for (size_t k = 1; k < parts; k++) th.emplace_back(run, k);
+  run(0);
+  for (auto& t : th) t.join();
+  if (err) std::rethrow_exception(err);
+  for (size_t c = 0; c < planes; c++)
+    for (size_t i = 0; i < n; i++) out[c * n + i] += one[i];
+}
+template <typename T>
+void BlockRadon2D<T>::row_sums(T* out, T alpha) const {
+  const radon2d::Geometry& g = geometry_;
+  const T* table = table_.data();
+  radon2d_plane_sums<T>(out, (size_t)g.ndet * (size_t)g.na, (size_t)g.planes, (size_t)std::max(g.nx, g.ny), [&](size_t p) {
+    return radon2d::RowSum<T>(table, g, (double)alpha, (int)(p / (size_t)g.ndet), (int)(p % (size_t)g.ndet));
+  });
+}
+template <typename T>
+void BlockRadon2D<T>::col_sums(T* out, T alpha) const {
+  const radon2d::Geometry& g = geometry_;
+  const T* table = table_.data();
+  radon2d_plane_sums<T>(out, (size_t)g.ny * (size_t)g.nx, (size_t)g.planes, (size_t)g.na * (size_t)(2 * g.m + 2), [&](size_t p) {
+    return radon2d::ColSum<T>(table, g, (double)alpha, (int)(p % (size_t)g.ny), (int)(p / (size_t)g.ny));
+  });
+}
+template <typename T>
+void BlockRadon2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
+  if (d_table_.size() != table_.size()) throw Exception("BlockRadon2D used before Initialize().");
+  static_assert(sizeof(prost_hip_radon2d_geometry) == sizeof(radon2d::Geometry), "records of prost_hip.h");
+  radon2d::Geometry g = geometry_;
+  g.transpose = transpose ? 1 : 0;
+  CheckHip(Api<T>::radon2d(reinterpret_cast<const prost_hip_radon2d_geometry*>(&g), d_table_.data(), r, x, acc ? 1 : 0, CurrentStream()), "radon2d");
+}
+template class BlockRadon2D<float>;
+template class BlockRadon2D<double>;
 
 // ---- the symmetrised gradient of TGV^2, without a matrix ----
 template <typename T>
