@@ -7,6 +7,7 @@
 #include "prost/linop/conv2d.hpp"
 #include "prost/linop/conv2d_strided.hpp"
 #include "prost/linop/radon2d.hpp"
+#include "prost/linop/sample2d.hpp"
 #include "prost/linop/sym_gradient2d.hpp"
 
 namespace prost {
@@ -301,6 +302,36 @@ class BlockRadon2D : public ProductBlock<T> {
   radon2d::Geometry geometry_;
   std::vector<T> table_;                   ///< the per-angle table as it is uploaded
   device_vector<T> d_table_;
+};
+
+/// bilinear resampling of L column-major planes of ny x nx at M positions (a warp by a flow field, a rotation or zoom, scattered
+/// samples; zero padding) and its exact transpose, without a matrix.  L M rows by L ny nx columns.  Arithmetic, order of operations and
+/// the bucket tables of the adjoint: prost/linop/sample2d.hpp.  No describe(): the block runs on the generic paths.  Stored on the
+/// device: the 2 M positions in T, M int32 sample indices sorted by cell and (ny + 1)(nx + 1) + 1 int32 cell offsets -- not O(1) per
+/// row as BlockRadon2D, but about a quarter of the two sides of the sparse matrix it stands for.
+template <typename T>
+class BlockSample2D : public ProductBlock<T> {
+ public:
+  /// checks every argument (messages start with "BlockSample2D: "); declared_rows / declared_cols < 0: no size was declared
+  static BlockSample2D<T>* Create(size_t row, size_t col, double nx, double ny, double L, const std::vector<double>& x, const std::vector<double>& y,
+                                  double declared_rows = -1, double declared_cols = -1);
+  virtual void Initialize();
+  virtual void Release();
+  virtual T row_sum(size_t row, T alpha) const;
+  virtual T col_sum(size_t col, T alpha) const;
+  virtual void row_sums(T* out, T alpha) const;
+  virtual void col_sums(T* out, T alpha) const;
+  virtual size_t gpu_mem_amount() const { return (pos_x_.size() + pos_y_.size()) * sizeof(T) + (order_.size() + cell_start_.size()) * sizeof(int32_t); }
+  const sample2d::Geometry& geometry() const { return geometry_; }
+
+ protected:
+  BlockSample2D(size_t row, size_t col, size_t nrows, size_t ncols) : ProductBlock<T>(row, col, nrows, ncols) {}
+  virtual void Product(T* res, const T* rhs, bool transpose, bool accumulate);
+  sample2d::Geometry geometry_;
+  std::vector<T> pos_x_, pos_y_;           ///< the positions rounded once to T
+  std::vector<int32_t> order_, cell_start_;  ///< sample2d::MakeBuckets
+  device_vector<T> d_pos_x_, d_pos_y_;
+  device_vector<int32_t> d_order_, d_cell_start_;
 };
 
 /// the symmetrised gradient of a vector field on L channels of an ny x nx grid, without a matrix: the second-order operator of TGV^2

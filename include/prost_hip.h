@@ -288,6 +288,33 @@ typedef struct prost_hip_radon2d_geometry {
 } prost_hip_radon2d_geometry;
 int prost_hip_radon2d_f32(const prost_hip_radon2d_geometry* geometry, const float* table, float* res, const float* rhs, int accumulate, void* stream);
 int prost_hip_radon2d_f64(const prost_hip_radon2d_geometry* geometry, const double* table, double* res, const double* rhs, int accumulate, void* stream);
+/* BlockSample2D (additions; ABI version unchanged; kernels_linop_sample2d.hip, arithmetic, order of operations and the bucket tables
+ * of the adjoint: prost/linop/sample2d.hpp): bilinear resampling K of `planes` column-major image planes of ny x nx at m positions per
+ * plane (sample i of plane c at i + c m), zero padding, and its exact transpose.  With j0 = floor(fx), ax = fx - j0, bx = 1 - ax and
+ * likewise i0, ay, by, row i holds by bx at (i0, j0), ay bx at (i0 + 1, j0), by ax at (i0, j0 + 1), ay ax at (i0 + 1, j0 + 1); an
+ * entry outside the image or with a weight of exactly 0 is absent:
+ *   transpose == 0:  res[i] = the present terms (w) rhs(pixel) in that order, from +0                             rhs: images
+ *   transpose != 0:  res(yy, xx) = the entries of that column times rhs[i], by cell (yy-1, xx-1), (yy, xx-1),     rhs: samples
+ *                    (yy-1, xx), (yy, xx) and by ascending i inside a cell, from +0
+ * The geometry record is a HOST pointer, read before the call returns.  pos_x, pos_y: m values of T each in device memory, already
+ * rounded to T.  Positions: ANY value of the position arrays, non-finite ones included, gives in-bounds accesses (a sample with
+ * !(fx >= -1 && fx < nx && fy >= -1 && fy < ny) has no entries).  Tables: order (m int32) and cell_start ((ny + 1)(nx + 1) + 1 int32)
+ * in device memory are trusted as made by prost::sample2d::MakeBuckets from the same positions.  accumulate != 0 stores res + value
+ * instead of value; an empty row and an empty column store (add) 0.  Any element offset of res and rhs is accepted.  Aliasing: res and
+ * rhs must NOT overlap, and neither overlaps the positions or the tables.  No atomics: a call repeats its bits.  Side effects: no
+ * allocation, copy or synchronisation.  Refused without a launch: a null pointer, nx or ny outside 1 .. 16384, m or planes below 1,
+ * m or nx ny of 2^31 or more. */
+typedef struct prost_hip_sample2d_geometry {
+  int32_t ny, nx;       /* image plane */
+  int32_t m;            /* samples per plane */
+  int32_t planes;
+  int32_t transpose;
+  int32_t reserved;     /* 0 */
+} prost_hip_sample2d_geometry;
+int prost_hip_sample2d_f32(const prost_hip_sample2d_geometry* geometry, const float* pos_x, const float* pos_y, const int32_t* order, const int32_t* cell_start,
+                           float* res, const float* rhs, int accumulate, void* stream);
+int prost_hip_sample2d_f64(const prost_hip_sample2d_geometry* geometry, const double* pos_x, const double* pos_y, const int32_t* order, const int32_t* cell_start,
+                           double* res, const double* rhs, int accumulate, void* stream);
 /* BlockSymGradient2D (additions; ABI version unchanged; kernels_linop_sym_gradient2d.hip, arithmetic and order of operations:
  * prost/linop/sym_gradient2d.hpp): the symmetrised gradient E of a vector field on L channels of an ny x nx grid, N = nx ny, pixel
  * (y, x) at p = y + x ny.  Domain, 2 L N values: vx_c[p] at c N + p, vy_c[p] at (L + c) N + p (the range layout of gradient2d).  Range,

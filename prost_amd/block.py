@@ -289,6 +289,53 @@ def radon2d(nx, ny, L, angles, ndet=None, spacing=1.0, shift=0.0):
     return lambda row, col, nrows, ncols: [["radon2d", row, col, data], sz]
 
 
+SAMPLE2D_MAX_SIDE = 16384
+
+
+def sample2d(nx, ny, L, x, y):
+    """Bilinear resampling of an image at M arbitrary positions, applied without a matrix, and its exact transpose.  Domain: L
+    column-major planes of ny x nx, element (yy, xx, c) at yy + xx ny + c nx ny.  Range: L planes of M samples, sample i of plane c at
+    i + c M, M = len(x) = len(y).  x[i], y[i] are pixel coordinates with the pixel centres at the integers (x along the nx axis); they
+    are rounded once to the precision of the problem.  Sample i is the bilinear interpolant of the four pixels around (y[i], x[i]);
+    pixels outside the image count as zero, and a position outside [-1, nx) x [-1, ny) gives a zero row.  A warp by a flow field
+    (dx, dy) is x = X + dx, y = Y + dy with X, Y the pixel grid in column-major order and M = nx ny.  The device stores the 2 M
+    positions, M int32 sample indices sorted by cell and (ny + 1)(nx + 1) + 1 int32 cell offsets: about a quarter of the two sides of
+    the sparse matrix.  Many samples inside one cell are correct but slow in the transpose."""
+    for name, v, top in (("nx", nx, SAMPLE2D_MAX_SIDE), ("ny", ny, SAMPLE2D_MAX_SIDE), ("L", L, None)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or int(v) != v:
+            raise ValueError("sample2d: %s = %r is not an integer" % (name, v))
+        if v < 1:
+            raise ValueError("sample2d: %s = %r has to be at least 1" % (name, v))
+        if top is not None and v > top:
+            raise ValueError("sample2d: %s = %r has to be at most %d" % (name, v, top))
+    nx, ny, L = int(nx), int(ny), int(L)
+    pos = []
+    for name, v in (("x", x), ("y", y)):
+        try:
+            if np.asarray(v).dtype.kind not in "iuf":
+                raise TypeError
+            v = np.array(v, dtype=np.float64, copy=True)
+        except (TypeError, ValueError):
+            raise ValueError("sample2d: %s has to be a vector of numbers" % name)
+        if v.ndim == 0:
+            v = v.reshape(1)
+        if v.ndim != 1:
+            raise ValueError("sample2d: %s has to be a vector, got shape %r" % (name, v.shape))
+        pos.append(v)
+    x, y = pos
+    if x.size != y.size:
+        raise ValueError("sample2d: %d x positions and %d y positions" % (x.size, y.size))
+    if x.size == 0:
+        raise ValueError("sample2d: the positions are empty")
+    if not (np.isfinite(x).all() and np.isfinite(y).all()):
+        raise ValueError("sample2d: the positions hold a non-finite value")
+    if x.size >= 2 ** 31 or L * x.size >= 2 ** 31:
+        raise ValueError("sample2d: M = %d samples on L = %d planes; M and L M have to stay below 2^31" % (x.size, L))
+    sz = [L * x.size, L * ny * nx]
+    data = [nx, ny, L, x, y]
+    return lambda row, col, nrows, ncols: [["sample2d", row, col, data], sz]
+
+
 SYM_GRADIENT2D_MAX_SIZE = 2 ** 53          # sizes travel as doubles
 
 

@@ -475,6 +475,17 @@ std::map<std::string, typename Factory<T>::BlockFactory>& Factory<T>::block_reg(
                                      std::vector<double>(pa->data.begin(), pa->data.begin() + pa->rows * pa->cols), GetScalarFromCell(d, 4), GetScalarFromCell(d, 5),
                                      GetScalarFromCell(d, 6), size.first, size.second);
     };
+    // bilinear resampling without a matrix: cells { nx, ny, L, x, y (full vectors of the same length) }; a caller that also knows the size it
+    // means the block to have appends { nrows, ncols } and gets it checked.  Every argument check is BlockSample2D<T>::Create's.
+    reg["sample2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
+      const auto size = declared_size(d, 5, "BlockSample2D: the data cells are { nx, ny, L, x, y } or { nx, ny, L, x, y, nrows, ncols }.");
+      const prost_value *px = d->cells[3], *py = d->cells[4];
+      if (!px || px->kind != PROST_VALUE_MATRIX || !py || py->kind != PROST_VALUE_MATRIX)
+        throw Exception("BlockSample2D: the positions have to be full vectors of type single or double.");
+      return BlockSample2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2),
+                                      std::vector<double>(px->data.begin(), px->data.begin() + px->rows * px->cols),
+                                      std::vector<double>(py->data.begin(), py->data.begin() + py->rows * py->cols), size.first, size.second);
+    };
     // the symmetrised gradient of TGV^2 without a matrix: cells { nx, ny, L, w }; a caller that also knows the size it means the block to
     // have appends { nrows, ncols } and gets it checked.  Every argument check is BlockSymGradient2D<T>::Create's.
     reg["sym_gradient2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {

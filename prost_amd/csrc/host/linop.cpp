@@ -760,6 +760,81 @@ void BlockRadon2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
 template class BlockRadon2D<float>;
 template class BlockRadon2D<double>;
 
+// ---- bilinear resampling at arbitrary positions, without a matrix ----
+template <typename T>
+BlockSample2D<T>* BlockSample2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, const std::vector<double>& x, const std::vector<double>& y,
+                                           double declared_rows, double declared_cols) {
+  namespace s2d = sample2d;
+  std::stringstream ss;
+  ss << "BlockSample2D: ";
+  const double kLimit = 2147483648.0;      // 2^31
+  for (const auto& v : {std::make_pair("nx", nx), std::make_pair("ny", ny)})
+    if (!(v.second >= 1) || v.second != std::floor(v.second) || v.second > s2d::kMaxSide) {
+      ss << v.first << " = " << v.second << " has to be an integer from 1 to " << s2d::kMaxSide << "."; throw Exception(ss.str());
+    }
+  if (!(L >= 1) || L != std::floor(L) || L >= kLimit) { ss << "L = " << L << " has to be a positive integer below 2^31."; throw Exception(ss.str()); }
+  if (x.size() != y.size()) { ss << x.size() << " x positions and " << y.size() << " y positions."; throw Exception(ss.str()); }
+  if (x.empty()) { ss << "the positions are empty."; throw Exception(ss.str()); }
+  const double m = (double)x.size();
+  if (m >= kLimit || L * m >= kLimit) { ss << "M = " << m << " samples on L = " << L << " planes; M and L M have to stay below 2^31."; throw Exception(ss.str()); }
+  for (size_t i = 0; i < x.size(); i++)
+    if (!std::isfinite(x[i]) || !std::isfinite(y[i])) { ss << "the positions hold a non-finite value."; throw Exception(ss.str()); }
+  const double rows = L * m, cols = L * ny * nx;
+  if ((declared_rows >= 0 || declared_cols >= 0) && (declared_rows != rows || declared_cols != cols)) {
+    ss << "the declared size " << declared_rows << " x " << declared_cols << " is not L M x L ny nx = " << rows << " x " << cols << "."; throw Exception(ss.str());
+  }
+  std::unique_ptr<BlockSample2D<T>> b(new BlockSample2D<T>(row, col, (size_t)rows, (size_t)cols));
+  b->geometry_ = s2d::MakeGeometry((long)ny, (long)nx, (long)x.size(), (long)L, false);
+  b->pos_x_.assign(x.begin(), x.end());            // rounded once to T
+  b->pos_y_.assign(y.begin(), y.end());
+  s2d::MakeBuckets<T>(b->pos_x_.data(), b->pos_y_.data(), x.size(), (int)ny, (int)nx, b->order_, b->cell_start_);
+  return b.release();
+}
+template <typename T>
+void BlockSample2D<T>::Initialize() { d_pos_x_ = pos_x_; d_pos_y_ = pos_y_; d_order_ = order_; d_cell_start_ = cell_start_; }
+template <typename T>
+void BlockSample2D<T>::Release() { d_pos_x_.clear(); d_pos_y_.clear(); d_order_.clear(); d_cell_start_.clear(); }
+template <typename T>
+T BlockSample2D<T>::row_sum(size_t row, T alpha) const {
+  return (T)sample2d::RowSum<T>(pos_x_.data(), pos_y_.data(), geometry_, (double)alpha, row % (size_t)geometry_.m);
+}
+template <typename T>
+T BlockSample2D<T>::col_sum(size_t col, T alpha) const {
+  const sample2d::Geometry& g = geometry_;
+  const size_t p = col % ((size_t)g.ny * (size_t)g.nx);
+  return (T)sample2d::ColSum<T>(pos_x_.data(), pos_y_.data(), order_.data(), cell_start_.data(), g, (double)alpha, (int)(p % (size_t)g.ny), (int)(p / (size_t)g.ny));
+}
+template <typename T>
+void BlockSample2D<T>::row_sums(T* out, T alpha) const {
+  const sample2d::Geometry& g = geometry_;
+  const size_t m = (size_t)g.m;
+  for (size_t i = 0; i < m; i++) {
+    const T s = (T)sample2d::RowSum<T>(pos_x_.data(), pos_y_.data(), g, (double)alpha, i);
+    for (size_t c = 0; c < (size_t)g.planes; c++) out[c * m + i] += s;
+  }
+}
+template <typename T>
+void BlockSample2D<T>::col_sums(T* out, T alpha) const {
+  const sample2d::Geometry& g = geometry_;
+  const size_t n = (size_t)g.ny * (size_t)g.nx;
+  for (size_t p = 0; p < n; p++) {
+    const T s = (T)sample2d::ColSum<T>(pos_x_.data(), pos_y_.data(), order_.data(), cell_start_.data(), g, (double)alpha, (int)(p % (size_t)g.ny), (int)(p / (size_t)g.ny));
+    for (size_t c = 0; c < (size_t)g.planes; c++) out[c * n + p] += s;
+  }
+}
+template <typename T>
+void BlockSample2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
+  if (d_pos_x_.size() != pos_x_.size() || d_cell_start_.size() != cell_start_.size()) throw Exception("BlockSample2D used before Initialize().");
+  static_assert(sizeof(prost_hip_sample2d_geometry) == sizeof(sample2d::Geometry), "records of prost_hip.h");
+  sample2d::Geometry g = geometry_;
+  g.transpose = transpose ? 1 : 0;
+  CheckHip(Api<T>::sample2d(reinterpret_cast<const prost_hip_sample2d_geometry*>(&g), d_pos_x_.data(), d_pos_y_.data(), d_order_.data(), d_cell_start_.data(), r, x,
+                            acc ? 1 : 0, CurrentStream()),
+           "sample2d");
+}
+template class BlockSample2D<float>;
+template class BlockSample2D<double>;
+
 // ---- the symmetrised gradient of TGV^2, without a matrix ----
 template <typename T>
 BlockSymGradient2D<T>* BlockSymGradient2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, double w, double declared_rows, double declared_cols) {
