@@ -6,6 +6,7 @@
 #include "prost/linop/block.hpp"
 #include "prost/linop/conv2d.hpp"
 #include "prost/linop/conv2d_strided.hpp"
+#include "prost/linop/fft2d.hpp"
 #include "prost/linop/radon2d.hpp"
 #include "prost/linop/sample2d.hpp"
 #include "prost/linop/sym_gradient2d.hpp"
@@ -332,6 +333,34 @@ class BlockSample2D : public ProductBlock<T> {
   std::vector<int32_t> order_, cell_start_;  ///< sample2d::MakeBuckets
   device_vector<T> d_pos_x_, d_pos_y_;
   device_vector<int32_t> d_order_, d_cell_start_;
+};
+
+/// the unitary 2-D discrete Fourier transform of L complex images of ny x nx (2 L real planes, real parts first) and its transpose, the
+/// unitary inverse transform, without a matrix: the operator of k-space data terms (MRI).  2 L N rows by 2 L N columns, N = nx ny, nx
+/// and ny powers of two up to 2048.  Arithmetic, order of operations, twiddle table and the closed-form sums: prost/linop/fft2d.hpp.
+/// No describe(): the block runs on the generic paths.  Stored on the device: the table (2 max(nx, ny) values) and one work buffer of
+/// 2 L N values between the two passes.
+template <typename T>
+class BlockFFT2D : public ProductBlock<T> {
+ public:
+  /// checks every argument (messages start with "BlockFFT2D: "); declared_rows / declared_cols < 0: no size was declared
+  static BlockFFT2D<T>* Create(size_t row, size_t col, double nx, double ny, double L, double declared_rows = -1, double declared_cols = -1);
+  virtual void Initialize();
+  virtual void Release();
+  virtual T row_sum(size_t row, T alpha) const;
+  virtual T col_sum(size_t col, T alpha) const { return row_sum(col, alpha); }      ///< the matrix is symmetric in (frequency, pixel)
+  virtual void row_sums(T* out, T alpha) const;              ///< one table of at most 12 class sums per call, one look-up per row
+  virtual void col_sums(T* out, T alpha) const { row_sums(out, alpha); }
+  virtual size_t gpu_mem_amount() const { return (table_.size() + this->nrows()) * sizeof(T); }
+  const fft2d::Geometry& geometry() const { return geometry_; }
+
+ protected:
+  BlockFFT2D(size_t row, size_t col, size_t nrows, size_t ncols) : ProductBlock<T>(row, col, nrows, ncols) {}
+  virtual void Product(T* res, const T* rhs, bool transpose, bool accumulate);
+  fft2d::Geometry geometry_;
+  std::vector<T> table_;                   ///< fft2d::MakeTable
+  double sums1_[fft2d::kMaxLog2 + 1];      ///< fft2d::SumTable at alpha = 1, made at creation: what row-by-row callers of row_sum ask for
+  device_vector<T> d_table_, d_work_;
 };
 
 /// the symmetrised gradient of a vector field on L channels of an ny x nx grid, without a matrix: the second-order operator of TGV^2

@@ -315,6 +315,27 @@ int prost_hip_sample2d_f32(const prost_hip_sample2d_geometry* geometry, const fl
                            float* res, const float* rhs, int accumulate, void* stream);
 int prost_hip_sample2d_f64(const prost_hip_sample2d_geometry* geometry, const double* pos_x, const double* pos_y, const int32_t* order, const int32_t* cell_start,
                            double* res, const double* rhs, int accumulate, void* stream);
+/* BlockFFT2D (additions; ABI version unchanged; kernels_linop_fft2d.hip, arithmetic, order of operations and the twiddle table:
+ * prost/linop/fft2d.hpp): the unitary 2-D discrete Fourier transform K of `planes` complex images of ny x nx and its transpose, the
+ * unitary inverse transform.  N = nx ny, pixel (y, x) at p = y + x ny, frequency (ky, kx) at q = ky + kx ny (DC at 0).  Domain and
+ * range, 2 planes N values each: re_c at c N, im_c at (planes + c) N.  s = 1 / sqrt(N):
+ *   transpose == 0:  res[ky, kx] = s sum rhs[y, x] exp(-2 pi i (ky y / ny + kx x / nx))
+ *   transpose != 0:  res[y, x]   = s sum rhs[ky, kx] exp(+2 pi i (ky y / ny + kx x / nx))
+ * as the radix-2 tree of fft2d.hpp: the y pass, then the x pass, then one multiplication by s rounded to T; a side of 1 has no pass.
+ * The geometry record is a HOST pointer, read before the call returns.  table: 2 max(nx, ny) values of T in device memory, as made by
+ * prost::fft2d::MakeTable<T>(max(nx, ny)).  work: 2 planes N values of T in device memory, overwritten when nx > 1 and ny > 1 (it holds
+ * the result of the y pass), untouched otherwise.  accumulate != 0 stores res + value instead of value.  Any element offset of res,
+ * rhs and work is accepted.  Aliasing: res, rhs and work must NOT overlap each other or the table.  Non-finite inputs stay inside
+ * their own plane pair (re_c, im_c) and cause no fault.  No atomics: a call repeats its bits.  Side effects: no allocation, copy or
+ * synchronisation.  Refused without a launch: a null pointer, nx or ny that is no power of two from 1 to 2048, planes below 1,
+ * 2 planes N of 2^31 or more. */
+typedef struct prost_hip_fft2d_geometry {
+  int32_t ny, nx;       /* image plane */
+  int32_t planes;       /* complex images */
+  int32_t transpose;
+} prost_hip_fft2d_geometry;
+int prost_hip_fft2d_f32(const prost_hip_fft2d_geometry* geometry, const float* table, float* work, float* res, const float* rhs, int accumulate, void* stream);
+int prost_hip_fft2d_f64(const prost_hip_fft2d_geometry* geometry, const double* table, double* work, double* res, const double* rhs, int accumulate, void* stream);
 /* BlockSymGradient2D (additions; ABI version unchanged; kernels_linop_sym_gradient2d.hip, arithmetic and order of operations:
  * prost/linop/sym_gradient2d.hpp): the symmetrised gradient E of a vector field on L channels of an ny x nx grid, N = nx ny, pixel
  * (y, x) at p = y + x ny.  Domain, 2 L N values: vx_c[p] at c N + p, vy_c[p] at (L + c) N + p (the range layout of gradient2d).  Range,

@@ -336,6 +336,36 @@ def sample2d(nx, ny, L, x, y):
     return lambda row, col, nrows, ncols: [["sample2d", row, col, data], sz]
 
 
+FFT2D_MAX_SIDE = 2048
+
+
+def fft2d(nx, ny, L=1):
+    """The unitary 2-D discrete Fourier transform of L complex images of ny x nx, applied without a matrix as a real 2 L N x 2 L N
+    operator, N = nx ny; its transpose is the unitary inverse transform, K^T K = I.  Domain: real parts first, re_c[p] at c N + p and
+    im_c[p] at (L + c) N + p with p = y + x ny -- the domain layout of gradient2d(nx, ny, 2 L), so gradient2d(nx, ny, 2) followed by
+    sum_norm2(4, False, ...) is the isotropic TV of one complex image.  Range: the same layout over frequencies q = ky + kx ny in
+    standard FFT order, DC at q = 0:  Y[ky, kx] = s sum X[y, x] exp(-2 pi i (ky y / ny + kx x / nx)), s = 1 / sqrt(nx ny).
+    nx and ny are powers of two from 1 to 2048 (a side of 1 makes the transform one-dimensional).  There is no sampling mask in the
+    block: a mask goes into the data term as a 0/1 coefficient, sum_1d("square", 1, d, mask, 0, 0) on v = F u, as in
+    examples/tv_mri.py.  The device holds a table of 2 max(nx, ny) values and one work buffer of 2 L N values.
+    Preconditioning: the row and column sums of |K|^alpha are known in closed form, but a diagonal preconditioner of a dense
+    orthogonal operator is very conservative (the sums are about 1.27 sqrt(N) at alpha = 1 where the operator's norm is 1): use
+    prob.set_scaling_identity(), as the example does."""
+    for name, v, top in (("nx", nx, FFT2D_MAX_SIDE), ("ny", ny, FFT2D_MAX_SIDE), ("L", L, None)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or int(v) != v:
+            raise ValueError("fft2d: %s = %r is not an integer" % (name, v))
+        if v < 1:
+            raise ValueError("fft2d: %s = %r has to be at least 1" % (name, v))
+        if top is not None and (v > top or int(v) & (int(v) - 1)):
+            raise ValueError("fft2d: %s = %r has to be a power of two from 1 to %d" % (name, v, top))
+    nx, ny, L = int(nx), int(ny), int(L)
+    if 2 * L * nx * ny >= 2 ** 31:
+        raise ValueError("fft2d: L = %d images of %d x %d; 2 L nx ny has to stay below 2^31" % (L, nx, ny))
+    sz = [2 * L * nx * ny, 2 * L * nx * ny]
+    data = [nx, ny, L]
+    return lambda row, col, nrows, ncols: [["fft2d", row, col, data], sz]
+
+
 SYM_GRADIENT2D_MAX_SIZE = 2 ** 53          # sizes travel as doubles
 
 

@@ -486,6 +486,12 @@ std::map<std::string, typename Factory<T>::BlockFactory>& Factory<T>::block_reg(
                                       std::vector<double>(px->data.begin(), px->data.begin() + px->rows * px->cols),
                                       std::vector<double>(py->data.begin(), py->data.begin() + py->rows * py->cols), size.first, size.second);
     };
+    // the unitary 2-D Fourier transform without a matrix: cells { nx, ny, L }; a caller that also knows the size it means the block to have
+    // appends { nrows, ncols } and gets it checked.  Every argument check is BlockFFT2D<T>::Create's.
+    reg["fft2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
+      const auto size = declared_size(d, 3, "BlockFFT2D: the data cells are { nx, ny, L } or { nx, ny, L, nrows, ncols }.");
+      return BlockFFT2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), size.first, size.second);
+    };
     // the symmetrised gradient of TGV^2 without a matrix: cells { nx, ny, L, w }; a caller that also knows the size it means the block to
     // have appends { nrows, ncols } and gets it checked.  Every argument check is BlockSymGradient2D<T>::Create's.
     reg["sym_gradient2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {

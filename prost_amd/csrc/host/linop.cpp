@@ -835,6 +835,61 @@ void BlockSample2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
 template class BlockSample2D<float>;
 template class BlockSample2D<double>;
 
+// ---- the unitary 2-D Fourier transform, without a matrix ----
+template <typename T>
+BlockFFT2D<T>* BlockFFT2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, double declared_rows, double declared_cols) {
+  std::stringstream ss;
+  ss << "BlockFFT2D: ";
+  const double kLimit = 2147483648.0;      // 2^31
+  for (const auto& v : {std::make_pair("nx", nx), std::make_pair("ny", ny)})
+    if (!(v.second >= 1) || v.second != std::floor(v.second) || v.second > fft2d::kMaxSide || !fft2d::IsSide((long)v.second)) {
+      ss << v.first << " = " << v.second << " has to be a power of two from 1 to " << fft2d::kMaxSide << "."; throw Exception(ss.str());
+    }
+  if (!(L >= 1) || L != std::floor(L) || L >= kLimit) { ss << "L = " << L << " has to be a positive integer below 2^31."; throw Exception(ss.str()); }
+  const double size = 2 * L * ny * nx;
+  if (size >= kLimit) { ss << "L = " << L << " images of " << nx << " x " << ny << "; 2 L nx ny has to stay below 2^31."; throw Exception(ss.str()); }
+  if ((declared_rows >= 0 || declared_cols >= 0) && (declared_rows != size || declared_cols != size)) {
+    ss << "the declared size " << declared_rows << " x " << declared_cols << " is not 2 L ny nx x 2 L ny nx = " << size << " x " << size << "."; throw Exception(ss.str());
+  }
+  std::unique_ptr<BlockFFT2D<T>> b(new BlockFFT2D<T>(row, col, (size_t)size, (size_t)size));
+  b->geometry_ = fft2d::MakeGeometry((long)ny, (long)nx, (long)L, false);
+  b->table_ = fft2d::MakeTable<T>(fft2d::TableSize((int)ny, (int)nx));
+  fft2d::SumTable((int)ny, (int)nx, 1.0, b->sums1_);
+  return b.release();
+}
+template <typename T>
+void BlockFFT2D<T>::Initialize() { d_table_ = table_; d_work_.resize(this->nrows(), (T)0); }
+template <typename T>
+void BlockFFT2D<T>::Release() { d_table_.clear(); d_work_.clear(); }
+template <typename T>
+T BlockFFT2D<T>::row_sum(size_t row, T alpha) const {
+  const fft2d::Geometry& g = geometry_;
+  const size_t q = row % ((size_t)g.ny * (size_t)g.nx);
+  const int l = fft2d::PeriodLog2((int)(q % (size_t)g.ny), (int)(q / (size_t)g.ny), g.ny, g.nx);
+  return (T)(alpha == (T)1 ? sums1_[l] : fft2d::ClassSum(g.ny, g.nx, (double)alpha, l));      // any other alpha: that one class, g terms
+}
+template <typename T>
+void BlockFFT2D<T>::row_sums(T* out, T alpha) const {
+  const fft2d::Geometry& g = geometry_;
+  double sums[fft2d::kMaxLog2 + 1];
+  fft2d::SumTable(g.ny, g.nx, (double)alpha, sums);
+  const size_t n = (size_t)g.ny * (size_t)g.nx;
+  for (size_t q = 0; q < n; q++) {
+    const T s = (T)sums[fft2d::PeriodLog2((int)(q % (size_t)g.ny), (int)(q / (size_t)g.ny), g.ny, g.nx)];
+    for (size_t c = 0; c < 2 * (size_t)g.planes; c++) out[c * n + q] += s;
+  }
+}
+template <typename T>
+void BlockFFT2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
+  if (d_table_.size() != table_.size() || d_work_.size() != this->nrows()) throw Exception("BlockFFT2D used before Initialize().");
+  static_assert(sizeof(prost_hip_fft2d_geometry) == sizeof(fft2d::Geometry), "records of prost_hip.h");
+  fft2d::Geometry g = geometry_;
+  g.transpose = transpose ? 1 : 0;
+  CheckHip(Api<T>::fft2d(reinterpret_cast<const prost_hip_fft2d_geometry*>(&g), d_table_.data(), d_work_.data(), r, x, acc ? 1 : 0, CurrentStream()), "fft2d");
+}
+template class BlockFFT2D<float>;
+template class BlockFFT2D<double>;
+
 // ---- the symmetrised gradient of TGV^2, without a matrix ----
 template <typename T>
 BlockSymGradient2D<T>* BlockSymGradient2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, double w, double declared_rows, double declared_cols) {
