@@ -49,4 +49,12 @@ PH_LW_HD constexpr bool lw_stores_y(int xa, int xb, int q) { return q >= xa && q
 // bytes of LDS per workgroup: (K - 1) links x 2 slots + the ring, planes of 1 KiB (y_1, y_2, x and, per pixel, b)
 PH_LW_HD constexpr int lw_lds_bytes(int K, int planes) { return (2 * (K - 1) + kLevelWaveRing) * planes * 1024; }
 
+// the shortest chunk in [lo, hi] whose workgroups (strips x chunks) all run in one round of `slots` resident workgroups; hi where
+// none does (such images run several rounds whatever the length).  A chunk of c columns runs c + 3K - 2 steps: shorter is cheaper.
+constexpr int lw_one_round_cols(long long nx, long long strips, long long slots = 1024, int lo = 6, int hi = 72) {
+  for (int c = lo; c <= hi; c++)
+    if (strips * ((nx + c - 1) / c) <= slots) return c;
+  return hi;
+}
+
 }  // namespace prost_hip

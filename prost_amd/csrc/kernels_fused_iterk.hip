@@ -386,10 +386,16 @@ __global__ void __launch_bounds__(kWave, WAVES)
 // the only return (rec->stop) is uniform and lies in front of the first barrier.
 // Loads: wave 1 alone issues the input ring (R = 3 columns, the batch of column p + 2 in front of the wait for column p) and reads
 // it; it stores nothing, so its vmcnt counts load batches only.  Wave K alone stores.
-template <int K, int GFN, bool BPTR>
+//
+// Placement (measured, docs/rounds/r26.md): workgroups b, b + 256, b + 512, b + 768 share a CU, and the hardware starts each of them
+// on the next SIMD, so with level = wave + 1 every SIMD already holds one wave of each level: the levels' idle steps (2 (l - 1) at the
+// start, 2 (K - l) at the end), wave 1's loads and wave K's stores are spread over the four SIMDs.  Rotating the levels by b / 256
+// undoes exactly that (one level per SIMD) and costs 5.7 % of a launch at 4096^2, so the assignment stays as it is.
+// PLACE (tools/iterk_levelwave_probe.py only): lane 0 of every wave records where it ran, after its last step, in place[b K + wave].
+template <int K, int GFN, bool BPTR, bool PLACE = false>
 __global__ void __launch_bounds__(K * kWave, 4)
     fused_iter2d_xkw_kernel(float* __restrict__ x_out, float* __restrict__ y_out, const float* __restrict__ x, const float* __restrict__ y,
-                            FusedArgs<float> a, const StepsK<K> sp, const PdhgRecord<float>* __restrict__ rec) {
+                            FusedArgs<float> a, const StepsK<K> sp, const PdhgRecord<float>* __restrict__ rec, unsigned* __restrict__ place) {
   static_assert(K >= 2 && K <= 4, "one halo lane per side: K <= 4");
   constexpr int VEC = 4, H = 1, R = kLevelWaveRing;
   typedef float T;
@@ -585,6 +591,10 @@ __global__ void __launch_bounds__(K * kWave, 4)
     step(int_c<0>(), t);
     if (t + 1 < steps) step(int_c<1>(), t + 1);
   }
+  if constexpr (PLACE) {          // HW_ID[15:0]: wave, SIMD, pipe, CU, SH, SE; XCC_ID[3:0] above them
+    const unsigned hw = __builtin_amdgcn_s_getreg((16 - 1) << 11 | 4), xcc = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20);
+    if (lane == 0) place[(size_t)blockIdx.x * K + (lvl - 1)] = hw | xcc << 16;
+  }
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
@@ -629,14 +639,20 @@ static bool iterk_levelwave(const prost_hip_fused_desc* d, int K, bool res) {
   return !(e && e[0] == '0' && e[1] == 0) && d->arith == PROST_HIP_ARITH_EXACT && !res && (K == 3 || K == 4);
 }
 
+// PROST_ITERK_LEVELWAVE_PLACE=1 (tools/iterk_levelwave_probe.py, read per launch): the workspace argument of a plain launch, unused
+// otherwise, receives the placement record: grid x K words
+static unsigned* iterk_place_record(void* ws) {
+  const char* p = getenv("PROST_ITERK_LEVELWAVE_PLACE");
+  return p && p[0] == '1' && p[1] == 0 ? static_cast<unsigned*>(ws) : nullptr;
+}
+
 static int iterk_chunk_cols(const prost_hip_fused_desc* d, int K, bool res, int cols) {
   const size_t rpw = (size_t)iterk_rows_per_wave(K), strips = (d->ny + rpw - 1) / rpw;
   if (cols <= 0 && iterk_levelwave(d, K, res)) {
     // a workgroup of K wavefronts holds 28 (K = 3) / 36 KiB (K = 4) of LDS: four per CU, 1024 on the chip, four wavefronts per SIMD.
-    // The shortest chunk whose workgroups all run in one round of four per CU (4096^2: 72 columns, 969 workgroups); a chunk of c
+    // The shortest chunk whose workgroups all run in one round of four per CU (4096^2: 69 columns, 1020 workgroups); a chunk of c
     // columns runs c + 3K - 2 steps, so short chunks pay more for the skew than the single-wave pipeline does.
-    cols = 72;
-    for (int c : {6, 9, 12, 18, 24, 30, 36, 42, 48, 60, 72}) if (strips * ((d->nx + c - 1) / c) <= 1024) { cols = c; break; }
+    cols = lw_one_round_cols((long long)d->nx, (long long)strips);
     static const char* const names[] = {"", "", "", "PROST_ITERK3_COLS", "PROST_ITERK4_COLS"};
     return iterk_override(names[K], cols);
   }
@@ -692,7 +708,16 @@ static int run_iterk(const prost_hip_fused_desc* d, float* x_out, float* y_out, 
     if (iterk_levelwave(d, K, out4 != nullptr)) {
       const dim3 blockw(K * kWave);
       const bool bpw = d->g_coeff_ptr[1] != nullptr;
-#define GOW(G, BP) PH_LAUNCH((fused_iter2d_xkw_kernel<K, G, BP>), grid, blockw, 0, s, x_out, y_out, x, y, a, sp, rec)
+      unsigned* const place = iterk_place_record(ws);
+      if (place && !(K == 4 && d->g_fn == PROST_FN_SQUARE && bpw)) { set_error("fused K-iteration launch: the placement record exists for K = 4, square, per-pixel b"); return 1; }
+#define GOW(G, BP) PH_LAUNCH((fused_iter2d_xkw_kernel<K, G, BP>), grid, blockw, 0, s, x_out, y_out, x, y, a, sp, rec, nullptr)
+      if constexpr (K == 4) {
+        if (place) {
+          PH_LAUNCH((fused_iter2d_xkw_kernel<4, PROST_FN_SQUARE, true, true>), grid, blockw, 0, s, x_out, y_out, x, y, a, sp, rec, place);
+          hipError_t e_ = hipGetLastError();
+          return e_ != hipSuccess ? fail(e_, "fused K-iteration kernel (level per wavefront, placement record)") : 0;
+        }
+      }
       if (d->g_fn == PROST_FN_SQUARE) { if (bpw) GOW(PROST_FN_SQUARE, true); else GOW(PROST_FN_SQUARE, false); }
       else { if (bpw) GOW(PROST_FN_ABS, true); else GOW(PROST_FN_ABS, false); }
 #undef GOW

@@ -1,6 +1,9 @@
 """Exact-class K-iteration launches through the kernel C ABI: time of one launch per (K, cols), against the plain pair launch.
 usage: iterk_levelwave_probe.py [N] [K,K,...] [cols,cols,...]      (PROST_ITERK_LEVELWAVE=0: the single-wave instances)
-Prints one line per (K, cols): ms per launch, us per iteration, and the two pair launches a launch of four replaces."""
+       iterk_levelwave_probe.py place [N]
+Prints one line per (K, cols): ms per launch, us per iteration, and the two pair launches a launch of four replaces.
+place: where the wavefronts of the K = 4 launch (square, per-pixel b, auto chunk length) ran -- every wave records its HW_ID and XCC_ID
+after its last step: workgroups per CU, which workgroups share a CU, wave -> SIMD, distinct levels per SIMD, launch against launch."""
 import ctypes as C
 import os
 import sys
@@ -15,25 +18,29 @@ if os.environ.get("PROST_HIP_LIB"):
     hip.LIB_PATH = os.environ["PROST_HIP_LIB"]
 
 
-def main(N=4096, ks=(3, 4), cols_list=(0,), iters=200):
-    hip.require_device()
+def _setup(N):
     dtype = np.float32
     n, m = N * N, 2 * N * N
     rng = np.random.default_rng(0)
     fh = synthetic.rof_image(N, N, seed=42).astype(dtype)
     xh = (fh + 0.05 * (rng.random(n).astype(dtype) - 0.5)).astype(dtype)
-    yh = ((rng.random(m) - 0.5) * 1.2).astype(dtype)
     f = hip.DeviceArray.from_host(fh)
     x = [hip.DeviceArray.from_host(xh), hip.DeviceArray.zeros(n, dtype)]
-    y = [hip.DeviceArray.from_host(yh), hip.DeviceArray.zeros(m, dtype)]
+    y = [hip.DeviceArray.from_host(((rng.random(m) - 0.5) * 1.2).astype(dtype)), hip.DeviceArray.zeros(m, dtype)]
     d = hip.FusedDesc(); d.is3d = 0; d.nx, d.ny, d.L = N, N, 1
     d.g_fn = hip.FN_ID["square"]; d.f_fn = hip.FN_ID["ind_leq0"]
-    gv = [1, 0, 10, 0, 0, 0, 0]; fv = [1, 1, 1, 0, 0, 0, 0]
-    for i in range(7):
-        d.g_coeff_val[i] = gv[i]; d.f_coeff_val[i] = fv[i]
+    for i, (g, fv) in enumerate(zip([1, 0, 10, 0, 0, 0, 0], [1, 1, 1, 0, 0, 0, 0])):
+        d.g_coeff_val[i] = g; d.f_coeff_val[i] = fv
     d.g_coeff_ptr[1] = f.ptr.value
     d.T_val, d.S_val = 0.25, 0.5
     d.arith = 0
+    return d, f, x, y
+
+
+def main(N=4096, ks=(3, 4), cols_list=(0,), iters=200):
+    hip.require_device()
+    dtype = np.float32
+    d, f, x, y = _setup(N)
     L_ = hip.lib()
     I2 = hip.fn("fused_iteration2", dtype)
     IK = L_.prost_hip_fused_iterationk_f32
@@ -63,7 +70,65 @@ def main(N=4096, ks=(3, 4), cols_list=(0,), iters=200):
                 N, k, cols, L_.prost_hip_fused_iterationk_chunk_cols(C.byref(d), 0, k, 0), t, 1e3 * t / k, 100 * (t / k - pair / 2) / (pair / 2)), flush=True)
 
 
+def _hist(values):
+    h = {}
+    for v in values:
+        h[v] = h.get(v, 0) + 1
+    return " ".join("%s:%d" % (k, h[k]) for k in sorted(h))
+
+
+def place(N=4096, K=4):
+    """the placement record of the real launch (PROST_ITERK_LEVELWAVE_PLACE=1: the workspace argument receives grid x K words)"""
+    hip.require_device()
+    d, f, x, y = _setup(N)
+    L_ = hip.lib()
+    IK = L_.prost_hip_fused_iterationk_f32
+    taus = (C.c_double * 4)(0.3, 0.29, 0.28, 0.27); sigmas = (C.c_double * 4)(1.0, 1.03, 1.06, 1.09); thetas = (C.c_double * 4)(0.9, 0.91, 0.92, 0.93)
+    cols = L_.prost_hip_fused_iterationk_chunk_cols(C.byref(d), 0, K, 0)
+    grid = -(-N // 248) * -(-N // cols)
+    os.environ["PROST_ITERK_LEVELWAVE_PLACE"] = "1"
+
+    def record(back_to_back):
+        rec = hip.DeviceArray.from_host(np.full(grid * K, 0xffffffff, np.uint32))
+        for i in range(back_to_back):
+            hip.check(IK(C.byref(d), K, x[(i + 1) % 2].ptr, y[(i + 1) % 2].ptr, x[i % 2].ptr, y[i % 2].ptr, taus, sigmas, thetas, 0, None, rec.ptr, None))
+        hip.sync()
+        w = rec.to_host().reshape(grid, K)
+        rec.free()
+        assert (w != 0xffffffff).all(), "waves without a record"
+        return w
+
+    runs = [("first launch", record(1)), ("second launch", record(1)), ("fifth of five back to back", record(5))]
+    first = runs[0][1]
+    for name, w in runs:
+        simd, cu = (w >> 4) & 3, (w >> 8) & 0xfff          # cu: CU, SH, SE of HW_ID and the XCC above them
+        print("N=%d K=%d cols=%d grid=%d, %s" % (N, K, cols, grid, name))
+        print("  waves of a workgroup on one CU: %s" % _hist(len(set(cu[b])) == 1 for b in range(grid)))
+        print("  (wave, SIMD) pairs: %s" % _hist("w%d@s%d" % (k, simd[b, k]) for b in range(grid) for k in range(K)))
+        print("  workgroup b on XCC: b %% 8 == XCC for %d of %d; XCCs seen: %s" % (sum(int((w[b, 0] >> 16) & 15) == b % 8 for b in range(grid)), grid, _hist(int((w[b, 0] >> 16) & 15) for b in range(grid))))
+        on = {}
+        for b in range(grid):
+            on.setdefault(int(cu[b, 0]), []).append(b)
+        print("  CUs used: %d; workgroups per CU: %s" % (len(on), _hist(len(v) for v in on.values())))
+        print("  differences of the workgroups that share a CU (to the lowest b): %s" % _hist(tuple(b - v[0] for b in v[1:]) for v in on.values() if len(v) == 4))
+        for c in sorted(on)[:4]:
+            print("    CU %03x: b = %s" % (c, on[c]))
+        levels = []
+        for c, v in on.items():
+            if len(v) == 4:
+                for sd in range(4):
+                    levels.append(len({k + 1 for b in v for k in range(K) if simd[b, k] == sd}))          # wave k carries level k + 1
+        share = sum(1 for v in levels if v >= 3) / max(1, len(levels))
+        print("  CUs with four workgroups: distinct levels per SIMD: %s; SIMDs with >= 3 levels: %.1f %%" % (_hist(levels), 100 * share))
+        if w is not first:
+            print("  against the first launch: same CU for %d of %d workgroups, same SIMD for %d of %d waves" % (
+                int((((first >> 8) & 0xfff)[:, 0] == cu[:, 0]).sum()), grid, int((((first >> 4) & 3) == simd).sum()), grid * K), flush=True)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "place":
+        place(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
+        sys.exit(0)
     N = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
     ks = tuple(int(v) for v in sys.argv[2].split(",")) if len(sys.argv) > 2 else (3, 4)
     cols = tuple(int(v) for v in sys.argv[3].split(",")) if len(sys.argv) > 3 else (0,)
