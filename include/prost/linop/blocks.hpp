@@ -10,6 +10,7 @@
 #include "prost/linop/radon2d.hpp"
 #include "prost/linop/sample2d.hpp"
 #include "prost/linop/sym_gradient2d.hpp"
+#include "prost/linop/wavelet2d.hpp"
 
 namespace prost {
 
@@ -361,6 +362,37 @@ class BlockFFT2D : public ProductBlock<T> {
   std::vector<T> table_;                   ///< fft2d::MakeTable
   double sums1_[fft2d::kMaxLog2 + 1];      ///< fft2d::SumTable at alpha = 1, made at creation: what row-by-row callers of row_sum ask for
   device_vector<T> d_table_, d_work_;
+};
+
+/// the orthogonal, periodised, separable multi-level wavelet transform of L planes of ny x nx and its transpose, the inverse transform,
+/// without a matrix: the operator of wavelet sparsity priors.  L N rows by L N columns, N = nx ny.  Arithmetic, order of operations,
+/// limits and the sums: prost/linop/wavelet2d.hpp.  No describe(): the block runs on the generic paths.  Stored on the device: one work
+/// buffer of wavelet2d::WorkSize values (5/16 L N in 2-D) for the low-low corners between the levels; the taps travel with each launch.
+template <typename T>
+class BlockWavelet2D : public ProductBlock<T> {
+ public:
+  /// checks every argument (messages start with "BlockWavelet2D: "); declared_rows / declared_cols < 0: no size was declared
+  static BlockWavelet2D<T>* Create(size_t row, size_t col, double nx, double ny, double L, const std::vector<double>& taps, double levels,
+                                   double declared_rows = -1, double declared_cols = -1);
+  virtual void Initialize();
+  virtual void Release();
+  virtual T row_sum(size_t row, T alpha) const;
+  virtual T col_sum(size_t col, T alpha) const;
+  virtual void row_sums(T* out, T alpha) const;
+  virtual void col_sums(T* out, T alpha) const;
+  virtual size_t gpu_mem_amount() const { return wavelet2d::WorkSize(geometry_) * sizeof(T); }
+  const wavelet2d::Geometry& geometry() const { return geometry_; }
+
+ protected:
+  BlockWavelet2D(size_t row, size_t col, size_t nrows, size_t ncols) : ProductBlock<T>(row, col, nrows, ncols) {}
+  virtual void Product(T* res, const T* rhs, bool transpose, bool accumulate);
+  void Tables(double alpha) const;         ///< the 1-D tables of both axes for this alpha, kept until another alpha is asked for
+  wavelet2d::Geometry geometry_;
+  std::vector<double> taps64_;             ///< the taps as given
+  std::vector<T> taps_;                    ///< rounded once to T
+  mutable double tables_alpha_ = -1;
+  mutable wavelet2d::AxisSums tables_y_, tables_x_;
+  device_vector<T> d_work_;
 };
 
 /// the symmetrised gradient of a vector field on L channels of an ny x nx grid, without a matrix: the second-order operator of TGV^2

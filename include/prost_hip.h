@@ -336,6 +336,38 @@ typedef struct prost_hip_fft2d_geometry {
 } prost_hip_fft2d_geometry;
 int prost_hip_fft2d_f32(const prost_hip_fft2d_geometry* geometry, const float* table, float* work, float* res, const float* rhs, int accumulate, void* stream);
 int prost_hip_fft2d_f64(const prost_hip_fft2d_geometry* geometry, const double* table, double* work, double* res, const double* rhs, int accumulate, void* stream);
+/* BlockWavelet2D (additions; ABI version unchanged; kernels_linop_wavelet2d.hip, arithmetic, order of operations, limits and the slots of
+ * the work buffer: prost/linop/wavelet2d.hpp): the orthogonal, periodised, separable multi-level discrete wavelet transform K (Mallat's
+ * pyramid) of `planes` real planes of ny x nx and its transpose, the inverse transform.  N = nx ny, pixel (y, x) of plane c at
+ * c N + y + x ny; the range has the same layout, the in-place quadrant layout with the approximation at the top left.  With the low-pass
+ * taps h[0 .. T-1] and g[t] = (-1)^t h[T-1-t], one level on a line of m values is
+ *   lo[k] = sum_t h[t] x[(2k + t) mod m],  hi[k] = sum_t g[t] x[(2k + t) mod m],  k < m/2, lows at 0 .. m/2-1, highs at m/2 .. m-1,
+ * each sum from +0 with t ascending, every product and sum rounded once.  Level l = 0 .. levels-1 acts on the corner (ny >> l) x (nx >> l):
+ * the y pass over its columns, then the x pass over its rows; a side of 1 stays 1 and has no pass.
+ *   transpose == 0:  res = K rhs
+ *   transpose != 0:  res = K^T rhs: the levels in reverse, in a level the x pass before the y pass; output n of a line is the sum from +0
+ *                    over t = n mod 2, n mod 2 + 2, .. < T of h[t] lo[k] and then g[t] hi[k], k = ((n - t) / 2) mod (m / 2)
+ * The geometry record and taps are HOST pointers, read before the call returns: taps holds the T low-pass taps already rounded to T (they
+ * travel to the kernels as an argument).  work: prost::wavelet2d::WorkSize values of T in device memory, planes (C(1) + C(2)) with C(j) the
+ * values of a plane's corner after j levels (5/16 planes N in 2-D); it holds the low-low corners between the levels, is overwritten when
+ * more than one launch is needed and is untouched otherwise.  accumulate != 0 stores res + value instead of value; every element of
+ * res is stored exactly once per call.  rhs is never written.  Any element offset of res, rhs and work is accepted.  Aliasing: res, rhs
+ * and work must NOT overlap.  Non-finite inputs stay inside their own plane and cause no fault.  No atomics: a call repeats its bits.
+ * Side effects: no allocation, copy or synchronisation.  A corner of at most 4096 values per plane is finished by one launch with a
+ * workgroup per plane (no_tail != 0: one launch per level throughout, the same bits).  Refused without a launch: a null pointer, planes or
+ * levels below 1, T odd or outside 2 .. 16, a side greater than 1 that is not divisible by 2^levels or with side / 2^(levels-1) < T, a
+ * plane of 1 x 1, planes N of 2^31 or more. */
+typedef struct prost_hip_wavelet2d_geometry {
+  int32_t ny, nx;       /* image plane */
+  int32_t planes;
+  int32_t levels;
+  int32_t ntaps;        /* T */
+  int32_t transpose;
+  int32_t no_tail;      /* 0 */
+  int32_t reserved;     /* 0 */
+} prost_hip_wavelet2d_geometry;
+int prost_hip_wavelet2d_f32(const prost_hip_wavelet2d_geometry* geometry, const float* taps, float* work, float* res, const float* rhs, int accumulate, void* stream);
+int prost_hip_wavelet2d_f64(const prost_hip_wavelet2d_geometry* geometry, const double* taps, double* work, double* res, const double* rhs, int accumulate, void* stream);
 /* BlockSymGradient2D (additions; ABI version unchanged; kernels_linop_sym_gradient2d.hip, arithmetic and order of operations:
  * prost/linop/sym_gradient2d.hpp): the symmetrised gradient E of a vector field on L channels of an ny x nx grid, N = nx ny, pixel
  * (y, x) at p = y + x ny.  Domain, 2 L N values: vx_c[p] at c N + p, vy_c[p] at (L + c) N + p (the range layout of gradient2d).  Range,

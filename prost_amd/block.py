@@ -366,6 +366,83 @@ def fft2d(nx, ny, L=1):
     return lambda row, col, nrows, ncols: [["fft2d", row, col, data], sz]
 
 
+WAVELET2D_MAX_TAPS = 16
+WAVELET2D_ORTHO_TOLERANCE = 1e-12
+
+
+def wavelet2d_taps(name):
+    """the float64 low-pass taps h of a named orthogonal wavelet ("haar", "db2", "db3"), from closed forms; g[t] = (-1)^t h[T-1-t]"""
+    if name == "haar":
+        d = np.sqrt(2.0)
+        return np.array([1.0 / d, 1.0 / d])
+    if name == "db2":
+        s, d = np.sqrt(3.0), 4.0 * np.sqrt(2.0)
+        return np.array([(1.0 + s) / d, (3.0 + s) / d, (3.0 - s) / d, (1.0 - s) / d])
+    if name == "db3":
+        a = np.sqrt(10.0)
+        b, d = np.sqrt(5.0 + 2.0 * a), 16.0 * np.sqrt(2.0)
+        return np.array([(1.0 + a + b) / d, (5.0 + a + 3.0 * b) / d, (10.0 - 2.0 * a + 2.0 * b) / d,
+                         (10.0 - 2.0 * a - 2.0 * b) / d, (5.0 + a - 3.0 * b) / d, (1.0 + a - b) / d])
+    raise ValueError("wavelet2d: the wavelet %r is not one of 'haar', 'db2', 'db3'; any other filter is given as its low-pass taps" % (name,))
+
+
+def wavelet2d(nx, ny, L=1, wavelet="haar", levels=1):
+    """The orthogonal, periodised, separable multi-level discrete wavelet transform (Mallat's pyramid) of L real planes of ny x nx,
+    applied without a matrix as a real L N x L N operator, N = nx ny; its transpose is the inverse transform, K^T K = I.  Pixel (y, x)
+    of plane c at c N + y + x ny, as in every other block; the range is the in-place quadrant layout with the approximation at the top
+    left, so wavelet2d(nx, ny, 2, ...) followed by sum_norm2(2, False, "abs", ...) is the l1-norm of the complex coefficients of the
+    image fft2d and gradient2d(nx, ny, 2) act on.  wavelet: "haar", "db2", "db3" (wavelet2d_taps) or the low-pass taps h of an
+    orthogonal filter of even length 2 .. 16; they are accepted if |sum_k h[k] h[k+2l] - delta_l| <= 1e-12 for every l (a table
+    truncated to ten digits is refused) and rounded once to the precision of the problem; g[t] = (-1)^t h[T-1-t].  One level of a line
+    of m values: lo[k] = sum_t h[t] x[(2k+t) mod m], hi[k] = sum_t g[t] x[(2k+t) mod m].  A side greater than 1 has to be divisible by
+    2^levels with side / 2^(levels-1) >= T, a side of 1 makes the transform one-dimensional, 1 x 1 is refused, L N < 2^31; sides need
+    not be powers of two.  The device holds one work buffer of 5/16 L N values (3/4 with a side of 1).
+    Preconditioning: the row and column sums of |K|^alpha are computed from the filter, but a diagonal preconditioner of an orthogonal
+    operator is conservative (the operator's norm is 1, the sums grow with the support of the coarse functions): use
+    prob.set_scaling_identity(), as examples/wavelet_mri.py does."""
+    for name, v in (("nx", nx), ("ny", ny), ("L", L), ("levels", levels)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or int(v) != v:
+            raise ValueError("wavelet2d: %s = %r is not an integer" % (name, v))
+        if v < 1:
+            raise ValueError("wavelet2d: %s = %r has to be at least 1" % (name, v))
+    nx, ny, L, levels = int(nx), int(ny), int(L), int(levels)
+    if isinstance(wavelet, str):
+        taps = wavelet2d_taps(wavelet)
+    else:
+        try:
+            if np.asarray(wavelet).dtype.kind not in "iuf":
+                raise TypeError
+            taps = np.array(wavelet, dtype=np.float64, copy=True)
+        except (TypeError, ValueError):
+            raise ValueError("wavelet2d: the wavelet has to be a name or a vector of taps")
+        if taps.ndim != 1:
+            raise ValueError("wavelet2d: the taps have to be a vector, got shape %r" % (taps.shape,))
+        if taps.size < 2 or taps.size > WAVELET2D_MAX_TAPS or taps.size % 2:
+            raise ValueError("wavelet2d: %d taps; the filter has to have an even number of taps from 2 to %d" % (taps.size, WAVELET2D_MAX_TAPS))
+        if not np.isfinite(taps).all():
+            raise ValueError("wavelet2d: the taps hold a non-finite value")
+        T = taps.size
+        defect = max(abs(float(np.dot(taps[:T - 2 * l], taps[2 * l:])) - (1.0 if l == 0 else 0.0)) for l in range(T // 2))
+        if not defect <= WAVELET2D_ORTHO_TOLERANCE:
+            raise ValueError("wavelet2d: the taps are not orthonormal: |sum_k h[k] h[k+2l] - delta_l| = %.3g for some l, above %g (taps "
+                             "rounded from exact values miss by about 1e-15; a table truncated to fewer digits is refused)" % (defect, WAVELET2D_ORTHO_TOLERANCE))
+    T = int(taps.size)
+    if nx == 1 and ny == 1:
+        raise ValueError("wavelet2d: a plane of 1 x 1 has nothing to transform")
+    for name, v in (("nx", nx), ("ny", ny)):
+        if v == 1:
+            continue
+        if levels > 30 or v % 2 ** levels:
+            raise ValueError("wavelet2d: %s = %d is not divisible by 2^levels = 2^%d" % (name, v, levels))
+        if v // 2 ** (levels - 1) < T:
+            raise ValueError("wavelet2d: %s = %d at %d levels: the coarsest line holds %d values, fewer than the filter's %d taps" % (name, v, levels, v // 2 ** (levels - 1), T))
+    if L * nx * ny >= 2 ** 31:
+        raise ValueError("wavelet2d: L = %d planes of %d x %d; L nx ny has to stay below 2^31" % (L, nx, ny))
+    sz = [L * nx * ny, L * nx * ny]
+    data = [nx, ny, L, taps, levels]
+    return lambda row, col, nrows, ncols: [["wavelet2d", row, col, data], sz]
+
+
 SYM_GRADIENT2D_MAX_SIZE = 2 ** 53          # sizes travel as doubles
 
 

@@ -492,6 +492,16 @@ std::map<std::string, typename Factory<T>::BlockFactory>& Factory<T>::block_reg(
       const auto size = declared_size(d, 3, "BlockFFT2D: the data cells are { nx, ny, L } or { nx, ny, L, nrows, ncols }.");
       return BlockFFT2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), size.first, size.second);
     };
+    // the orthogonal multi-level wavelet transform without a matrix: cells { nx, ny, L, taps (full vector, the low-pass filter), levels }; a
+    // caller that also knows the size it means the block to have appends { nrows, ncols } and gets it checked.  Every argument check is
+    // BlockWavelet2D<T>::Create's.
+    reg["wavelet2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
+      const auto size = declared_size(d, 5, "BlockWavelet2D: the data cells are { nx, ny, L, taps, levels } or { nx, ny, L, taps, levels, nrows, ncols }.");
+      const prost_value* pt = d->cells[3];
+      if (!pt || pt->kind != PROST_VALUE_MATRIX) throw Exception("BlockWavelet2D: the taps have to be a full vector of type single or double.");
+      return BlockWavelet2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2),
+                                       std::vector<double>(pt->data.begin(), pt->data.begin() + pt->rows * pt->cols), GetScalarFromCell(d, 4), size.first, size.second);
+    };
     // the symmetrised gradient of TGV^2 without a matrix: cells { nx, ny, L, w }; a caller that also knows the size it means the block to
     // have appends { nrows, ncols } and gets it checked.  Every argument check is BlockSymGradient2D<T>::Create's.
     reg["sym_gradient2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {

@@ -36,6 +36,7 @@ template <typename T> struct Api;
     static constexpr auto radon2d = prost_hip_radon2d_##S; \
     static constexpr auto sample2d = prost_hip_sample2d_##S; \
     static constexpr auto fft2d = prost_hip_fft2d_##S; \
+    static constexpr auto wavelet2d = prost_hip_wavelet2d_##S; \
     static constexpr auto linop_sym_gradient2d = prost_hip_linop_sym_gradient2d_##S; \
     static constexpr auto prox_elem = prost_hip_prox_elem_##S;                    \
     static constexpr auto prox_elem_moreau = prost_hip_prox_elem_moreau_##S;      \

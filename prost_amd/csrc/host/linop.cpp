@@ -890,6 +890,90 @@ void BlockFFT2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
 template class BlockFFT2D<float>;
 template class BlockFFT2D<double>;
 
+// ---- the orthogonal multi-level wavelet transform, without a matrix ----
+template <typename T>
+BlockWavelet2D<T>* BlockWavelet2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, const std::vector<double>& taps, double levels,
+                                             double declared_rows, double declared_cols) {
+  namespace w2d = wavelet2d;
+  std::stringstream ss;
+  ss << "BlockWavelet2D: ";
+  for (double v : taps)
+    if (!std::isfinite(v)) { ss << "the taps hold a non-finite value."; throw Exception(ss.str()); }
+  if (const char* why = w2d::CheckShape(ny, nx, L, levels, (double)taps.size())) {
+    ss << why << " (nx = " << nx << ", ny = " << ny << ", L = " << L << ", levels = " << levels << ", " << taps.size() << " taps)."; throw Exception(ss.str());
+  }
+  const double defect = w2d::OrthoDefect(taps.data(), (int)taps.size());
+  if (!(defect <= w2d::kOrthoTolerance)) {
+    ss << "the taps are not orthonormal: |sum_k h[k] h[k+2l] - delta_l| = " << defect << " for some l, above " << w2d::kOrthoTolerance
+       << " (taps rounded from exact values miss by about 1e-15; a table truncated to fewer digits is refused)."; throw Exception(ss.str());
+  }
+  const double size = L * ny * nx;
+  if ((declared_rows >= 0 || declared_cols >= 0) && (declared_rows != size || declared_cols != size)) {
+    ss << "the declared size " << declared_rows << " x " << declared_cols << " is not L ny nx x L ny nx = " << size << " x " << size << "."; throw Exception(ss.str());
+  }
+  std::unique_ptr<BlockWavelet2D<T>> b(new BlockWavelet2D<T>(row, col, (size_t)size, (size_t)size));
+  b->geometry_ = w2d::MakeGeometry((long)ny, (long)nx, (long)L, (long)levels, (long)taps.size(), false);
+  b->taps64_ = taps;
+  b->taps_.assign(taps.begin(), taps.end());           // rounded once to T
+  return b.release();
+}
+template <typename T>
+void BlockWavelet2D<T>::Initialize() { d_work_.resize(wavelet2d::WorkSize(geometry_), (T)0); }
+template <typename T>
+void BlockWavelet2D<T>::Release() { d_work_.clear(); }
+template <typename T>
+void BlockWavelet2D<T>::Tables(double alpha) const {
+  if (tables_alpha_ == alpha) return;
+  const wavelet2d::Geometry& g = geometry_;
+  tables_y_ = wavelet2d::AxisTables(g.ny, g.levels, taps64_.data(), g.ntaps, alpha);
+  tables_x_ = wavelet2d::AxisTables(g.nx, g.levels, taps64_.data(), g.ntaps, alpha);
+  tables_alpha_ = alpha;
+}
+template <typename T>
+T BlockWavelet2D<T>::row_sum(size_t row, T alpha) const {
+  const wavelet2d::Geometry& g = geometry_;
+  Tables((double)alpha);
+  const size_t q = row % ((size_t)g.ny * (size_t)g.nx);
+  return (T)wavelet2d::RowSum(g, tables_y_, tables_x_, (int)(q % (size_t)g.ny), (int)(q / (size_t)g.ny));
+}
+template <typename T>
+T BlockWavelet2D<T>::col_sum(size_t col, T alpha) const {
+  const wavelet2d::Geometry& g = geometry_;
+  Tables((double)alpha);
+  const size_t p = col % ((size_t)g.ny * (size_t)g.nx);
+  return (T)wavelet2d::ColSum(g, tables_y_, tables_x_, (int)(p % (size_t)g.ny), (int)(p / (size_t)g.ny));
+}
+template <typename T>
+void BlockWavelet2D<T>::row_sums(T* out, T alpha) const {
+  const wavelet2d::Geometry& g = geometry_;
+  Tables((double)alpha);
+  const size_t n = (size_t)g.ny * (size_t)g.nx;
+  for (size_t q = 0; q < n; q++) {
+    const T s = (T)wavelet2d::RowSum(g, tables_y_, tables_x_, (int)(q % (size_t)g.ny), (int)(q / (size_t)g.ny));
+    for (size_t c = 0; c < (size_t)g.planes; c++) out[c * n + q] += s;
+  }
+}
+template <typename T>
+void BlockWavelet2D<T>::col_sums(T* out, T alpha) const {
+  const wavelet2d::Geometry& g = geometry_;
+  Tables((double)alpha);
+  const size_t n = (size_t)g.ny * (size_t)g.nx;
+  for (size_t p = 0; p < n; p++) {
+    const T s = (T)wavelet2d::ColSum(g, tables_y_, tables_x_, (int)(p % (size_t)g.ny), (int)(p / (size_t)g.ny));
+    for (size_t c = 0; c < (size_t)g.planes; c++) out[c * n + p] += s;
+  }
+}
+template <typename T>
+void BlockWavelet2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
+  if (d_work_.size() != wavelet2d::WorkSize(geometry_)) throw Exception("BlockWavelet2D used before Initialize().");
+  static_assert(sizeof(prost_hip_wavelet2d_geometry) == sizeof(wavelet2d::Geometry), "records of prost_hip.h");
+  wavelet2d::Geometry g = geometry_;
+  g.transpose = transpose ? 1 : 0;
+  CheckHip(Api<T>::wavelet2d(reinterpret_cast<const prost_hip_wavelet2d_geometry*>(&g), taps_.data(), d_work_.data(), r, x, acc ? 1 : 0, CurrentStream()), "wavelet2d");
+}
+template class BlockWavelet2D<float>;
+template class BlockWavelet2D<double>;
+
 // ---- the symmetrised gradient of TGV^2, without a matrix ----
 template <typename T>
 BlockSymGradient2D<T>* BlockSymGradient2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, double w, double declared_rows, double declared_cols) {
