@@ -107,6 +107,50 @@ __device__ __forceinline__ void div_to_float_exact_vec(const float (&x)[VEC], co
     }
   }
 }
+// The same on PAIRS of floats (two rows of a lane in an aligned register pair; the level-per-wavefront kernel keeps its columns that
+// way): the same q0, the same window, the same fallback.  The two guards of the NP x 2 quotients of a lane are folded with integer
+// min / max before ONE compare each, instead of two compares per element:
+//   * tie window: low in [2^28 - 4, 2^28 + 4] for the 29 dropped bits `low` of q0  <=>  (lo32(q0) << 3) - (2^28 - 4) * 8 <= 64 as
+//     unsigned (the shift drops the three bits above `low`; low * 8 < 2^32), and "any element inside" <=> the MINIMUM is <= 64;
+//   * not a normal float: with t = bits(out) << 1 (sign dropped, biased exponent in the top byte) out is normal <=> t in
+//     [0x01000000, 0xFEFFFFFF] <=> t - 0x01000000 <= 0xFDFFFFFF as unsigned, and "any element not normal" <=> the MAXIMUM is above.
+// Both are the scalar form's conditions exactly.  Even if they were not, the guards only SELECT the path: the full division is the
+// definition of the result, and the fast quotient of an element outside the window that is a normal float equals it (above), so
+// whichever path a wave takes writes the same bits.
+typedef float native_f2 __attribute__((ext_vector_type(2)));
+template <int NP>
+__device__ __forceinline__ void div_to_float_exact_vec(const native_f2 (&x)[NP], const UniformDiv& u, native_f2 (&out)[NP]) {
+  unsigned wmin = 0xFFFFFFFFu, tmax = 0u;
+#pragma unroll
+  for (int p = 0; p < NP; p++)
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      const double q0 = (double)x[p][h] * u.rD;
+      const float o = (float)q0;
+      out[p][h] = o;
+      wmin = min(wmin, ((unsigned)((unsigned long long)__double_as_longlong(q0)) << 3) - (((1u << 28) - 4u) << 3));
+      tmax = max(tmax, ((unsigned)__float_as_int(o) << 1) - 0x01000000u);
+    }
+  const unsigned long long odd = __builtin_amdgcn_ballot_w64(wmin <= 64u) | __builtin_amdgcn_ballot_w64(tmax > 0xFDFFFFFFu);
+  if (__builtin_expect(odd != 0, 0)) {
+    // second look (rare; always taken by waves with padding lanes, whose x is 0): a zero result of a zero x is exact
+    unsigned long long slow = 0;
+#pragma unroll
+    for (int p = 0; p < NP; p++)
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const double q0 = (double)x[p][h] * u.rD;
+        const unsigned low = (unsigned)((unsigned long long)__double_as_longlong(q0)) & 0x1FFFFFFFu;
+        slow |= __builtin_amdgcn_ballot_w64((low - ((1u << 28) - 4u)) <= 8u || (!__builtin_isnormal((float)out[p][h]) && x[p][h] != 0.0f));
+      }
+    if (slow != 0) {
+#pragma unroll
+      for (int p = 0; p < NP; p++)
+#pragma unroll
+        for (int h = 0; h < 2; h++) out[p][h] = (float)((double)x[p][h] / u.D);
+    }
+  }
+}
 // fp64: the short quotient for every element, the range guard as a wave mask, the full division for the whole wave if any lane needs it
 template <int VEC>
 __device__ __forceinline__ void div_to_float_exact_vec(const double (&x)[VEC], const UniformDiv& u, double (&out)[VEC]) {
@@ -325,6 +369,59 @@ __device__ __forceinline__ void norm2_leq0_fast(const T (&nv)[VEC], const T (&av
 #pragma unroll
       for (int i = 0; i < NC; i++) { const T q = pr * av[i][j] / nrm; out[i][j] = nz ? q : (T)0; }
     }
+  }
+}
+// fp32, SHARE = true, on PAIRS (nv[p], av[i][p], out[i][p]: rows 2p, 2p + 1 of the lane in an aligned register pair): the same mid /
+// general split, the same operations on the same operands -- element (p, h) is element j = 2p + h of the form above, and the
+// reciprocals of pair p come from the one seed rcp_refined_pairs gives elements 2p, 2p + 1.  What differs is where the values sit:
+// the operations that are the same for both rows of a pair (the radius terms, the products pr * v) are written on the pair, and
+// nothing is moved between the caller's registers and the prox's.
+template <int NC, int NP>
+__device__ __forceinline__ void norm2_leq0_fast(const native_f2 (&nv)[NP], const native_f2 (&av)[NC][NP], float b, bool tiny_is_zero, native_f2 (&out)[NC][NP]) {
+  constexpr float kLo = 1.2621774483536189e-29f;             // 2^-96
+  unsigned nmax = 0;                                         // bit patterns: see above
+#pragma unroll
+  for (int p = 0; p < NP; p++) nmax = max(nmax, max((unsigned)__float_as_int(nv[p][0]), (unsigned)__float_as_int(nv[p][1])));
+  bool mid = nmax <= 0x7E800000u;                            // 2^126
+  if (!tiny_is_zero) {
+    unsigned tmin = 0xFFFFFFFFu;
+#pragma unroll
+    for (int p = 0; p < NP; p++) tmin = min(tmin, min((unsigned)__float_as_int(nv[p][0]) - 1u, (unsigned)__float_as_int(nv[p][1]) - 1u));
+    mid = mid && tmin >= (unsigned)__float_as_int(kLo) - 1u;
+  }
+  if (__builtin_expect(mid, 1)) {
+    const native_f2 b2 = {b, b};
+    native_f2 nrm[NP];
+    double r[NP][2];
+#pragma unroll
+    for (int p = 0; p < NP; p++)
+#pragma unroll
+      for (int h = 0; h < 2; h++) nrm[p][h] = sqrt_midrange(nv[p][h] > kLo ? nv[p][h] : kLo);
+#pragma unroll
+    for (int p = 0; p < NP; p++) rcp_refined2(nrm[p][0], nrm[p][1], RcpSeedF64(), r[p][0], r[p][1]);
+#pragma unroll
+    for (int p = 0; p < NP; p++) {
+      const native_f2 t = nrm[p] - b2;
+      const native_f2 pr = native_f2{min0(t[0]), min0(t[1])} + b2;
+#pragma unroll
+      for (int i = 0; i < NC; i++) {
+        const native_f2 num = pr * av[i][p];
+        out[i][p] = native_f2{mul_rcp_pz(num[0], r[p][0]), mul_rcp_pz(num[1], r[p][1])};
+      }
+    }
+  } else {
+    // general expansions, still branch-free
+#pragma unroll
+    for (int p = 0; p < NP; p++)
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const bool nz = nv[p][h] > 0;
+        const float nrm = nz ? t_sqrt(nv[p][h]) : 1.0f;
+        const float t = nrm - b;
+        const float pr = (t > 0.0f ? 0.0f : t) + b;
+#pragma unroll
+        for (int i = 0; i < NC; i++) { const float q = pr * av[i][p][h] / nrm; out[i][p][h] = nz ? q : 0.0f; }
+      }
   }
 }
 constexpr float kTinyIsZeroRadius = 9.5367431640625e-07f;     // 2^-20

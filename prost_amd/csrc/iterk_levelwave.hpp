@@ -1,4 +1,4 @@
-// iterk_levelwave.hpp -- index rules of the level-per-wavefront K-iteration kernel (fused_iter2d_xkw_kernel, kernels_fused_iterk.hip).
+// iterk_levelwave.hpp -- index rules of the level-per-wavefront K-iteration kernel (fused_iter2d_xkw_kernel, kernels_fused_iterk_lw.hip).
 //
 // Plain C++ (host and device): the kernel, the launcher and tests/host/iterk_levelwave_harness.cpp follow this one definition.
 //

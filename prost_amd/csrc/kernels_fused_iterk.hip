@@ -22,40 +22,10 @@
 //
 // Arithmetic: the tolerance-class forms of the pair kernel (fused multiply-adds, fp32 reciprocal of 1 + step, v_rsq_f32).  A
 // K-launch equals K/2 pair launches of that class bit for bit (same expressions, same order; tests/test_gpu_fmad.py).
-#include "fused_common.hpp"
-#include "iterk_levelwave.hpp"
+#include "iterk_common.hpp"
 #include "reduce.hpp"
 
-#include <type_traits>
-
-#ifndef ITERK_NT
-#define ITERK_NT true
-#endif
-#ifndef ITERK_LOAD_AUX
-#define ITERK_LOAD_AUX 0
-#endif
-
 namespace prost_hip {
-
-typedef int idx_t;
-typedef __attribute__((address_space(3))) void lds_void_k;
-typedef const __attribute__((address_space(1))) void glb_void_k;
-
-struct LevelStep {
-  float tauT, rD, step, sigS, theta, opt;       // tau T, 1 / (1 + step), step = c a^2 tau T, sigma S, theta, 1 + theta
-  UniformDiv sq;                                // exact class: the divisor 1. + step of Function1DSquare and its reciprocal, in double
-};
-template <int K>
-struct StepsK {
-  LevelStep s[K];
-  float tau_last, sigma_last;                   // residual transforms of the last iteration
-};
-
-template <int N> using int_c = std::integral_constant<int, N>;
-template <int A, int B, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (A < B) { f(int_c<A>()); static_for<A + 1, B>(f); }
-}
 
 template <int R, int NB, int STORES>
 __device__ __forceinline__ void ring_wait(bool steady, bool full) {
@@ -77,8 +47,8 @@ __device__ __forceinline__ void ring_wait(bool steady, bool full) {
 // the tolerance-class arithmetic.  With the exact forms (~71 VALU per pixel-iteration against ~17) THIS kernel, one wavefront carrying
 // all 2K stages, is bound by instruction issue: 128 / 166 / 203 VGPRs leave 4 / 3 / 2 wavefronts per SIMD, measured at 4096^2, K = 2 / 3 / 4:
 // 0.106 / 0.145 / 0.204 ms per launch = 53 / 48 / 51 us per iteration, no better than the pair kernel.  That is a property of the
-// single-wave pipeline, not of the arithmetic: plain exact launches of K = 3 and 4 run fused_iter2d_xkw_kernel below (one level per
-// wavefront, 0.154 / 0.178 ms), which the host uses for one launch of four in place of two plain pairs.
+// single-wave pipeline, not of the arithmetic: plain exact launches of K = 3 and 4 run fused_iter2d_xkw_kernel (one level per wavefront,
+// kernels_fused_iterk_lw.hip: 0.154 / 0.178 ms), which the host uses for one launch of four in place of two plain pairs.
 template <int K, int GFN, bool BPTR, bool RES, int R, int WAVES, bool EXACT>
 __global__ void __launch_bounds__(kWave, WAVES)
     fused_iter2d_xk_kernel(float* __restrict__ x_out, float* __restrict__ y_out, const float* __restrict__ x, const float* __restrict__ y,
@@ -371,232 +341,6 @@ __global__ void __launch_bounds__(kWave, WAVES)
   }
 }
 
-// ---- one level per wavefront (exact class, plain launches, K = 3 and 4) -------------------------------------------------------
-// The single-wave exact instances above hold all 2K stages in one wavefront's registers: 166 / 203 VGPRs at K = 3 / 4 leave 3 / 2
-// wavefronts per SIMD, too few to keep the VALU issuing (a lone wave issues every ~5 cycles), so their exact arithmetic -- 16-20 us
-// of VALU work per iteration at 4096^2 -- lies open on top of the memory time.  Here a workgroup is K wavefronts on one (strip,
-// chunk), wave l carries level l (the stage pair P_l, D_l of `step` above, same expressions, same operands: the bits are those of
-// the single-wave instance, the pair kernel and the oracle) and hands each finished column to wave l + 1 through LDS.  A wave holds
-// the state of ONE iteration, so four waves per SIMD stay resident and the arithmetic of the K iterations runs on all four SIMDs,
-// while the launch still reads x, y, b once and writes x, y once per K iterations.  Index rules: iterk_levelwave.hpp.
-//
-// Synchronisation: per step one s_waitcnt lgkmcnt(0) + s_barrier (a raw barrier: wave 1's LDS-DMA batches stay in flight across
-// it).  A wave reads link slot (t - 1) & 1 and writes slot t & 1, so the only writer of a slot and its only reader are always
-// separated by a barrier in both directions.  Every wave of a workgroup runs lw_steps() steps whatever its level, rows or columns;
-// the only return (rec->stop) is uniform and lies in front of the first barrier.
-// Loads: wave 1 alone issues the input ring (R = 3 columns, the batch of column p + 2 in front of the wait for column p) and reads
-// it; it stores nothing, so its vmcnt counts load batches only.  Wave K alone stores.
-//
-// Placement (measured, docs/rounds/r26.md): workgroups b, b + 256, b + 512, b + 768 share a CU, and the hardware starts each of them
-// on the next SIMD, so with level = wave + 1 every SIMD already holds one wave of each level: the levels' idle steps (2 (l - 1) at the
-// start, 2 (K - l) at the end), wave 1's loads and wave K's stores are spread over the four SIMDs.  Rotating the levels by b / 256
-// undoes exactly that (one level per SIMD) and costs 5.7 % of a launch at 4096^2, so the assignment stays as it is.
-// PLACE (tools/iterk_levelwave_probe.py only): lane 0 of every wave records where it ran, after its last step, in place[b K + wave].
-template <int K, int GFN, bool BPTR, bool PLACE = false>
-__global__ void __launch_bounds__(K * kWave, 4)
-    fused_iter2d_xkw_kernel(float* __restrict__ x_out, float* __restrict__ y_out, const float* __restrict__ x, const float* __restrict__ y,
-                            FusedArgs<float> a, const StepsK<K> sp, const PdhgRecord<float>* __restrict__ rec, unsigned* __restrict__ place) {
-  static_assert(K >= 2 && K <= 4, "one halo lane per side: K <= 4");
-  constexpr int VEC = 4, H = 1, R = kLevelWaveRing;
-  typedef float T;
-  typedef native_f4 V4;
-  if (rec && rec->stop) return;
-  const int lvl = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave)) + 1;      // 1 .. K, wave-uniform
-  LevelStep P = sp.s[0];
-  static_for<1, K>([&](auto L) { if (lvl - 1 == decltype(L)::value) P = sp.s[decltype(L)::value]; });
-  if (rec) {                       // device-resident step sizes: the same for every iteration of the launch
-    P.tauT = rec->p.tau * a.Tval; P.rD = (float)rec->p.ug.sq.rD; P.step = rec->p.ug.step; P.sigS = rec->p.sigma * a.Sval;
-    P.theta = rec->p.theta; P.opt = 1 + rec->p.theta; P.sq = rec->p.ug.sq;
-  }
-  const idx_t nx = (idx_t)a.nx, ny = (idx_t)a.ny;
-  const int lane = threadIdx.x & (kWave - 1);
-  const unsigned total = gridDim.x, chunks = a.chunks;
-  const unsigned xcd = blockIdx.x % 8u, q8 = blockIdx.x / 8u;          // XCD-aware tile order (kernels_fused_iter.hip)
-  const unsigned tile = xcd * (total / 8u) + (xcd < total % 8u ? xcd : total % 8u) + q8;
-  const unsigned strip = a.strips ? tile % a.strips : tile / chunks, chunk = a.strips ? tile / a.strips : tile % chunks;
-  const idx_t row0 = (idx_t)strip * kLevelWaveRows + ((idx_t)lane - H) * VEC;
-  const bool active = row0 >= 0 && row0 < ny;
-  const bool owner = active && lane >= H && lane < kWave - H;
-  const idx_t xa = (idx_t)chunk * a.cols_per_block;
-  const idx_t xb = xa + a.cols_per_block < nx ? xa + a.cols_per_block : nx;
-  const size_t N = (size_t)nx * (size_t)ny;
-  constexpr int NB = 3 + (BPTR ? 1 : 0);
-  constexpr int kSlot = NB * 1024;                 // one column: planes y_1, y_2, x (, b) of 64 lanes x 16 bytes
-  // [ring: R slots][link 1: 2 slots] .. [link K - 1: 2 slots]; link l is written by wave l and read by wave l + 1
-  __shared__ __attribute__((aligned(16))) char lds[lw_lds_bytes(K, NB)];
-  const T* const y2base = y + N;
-  T* const y2out = y_out + N;
-  const T* const bptr = BPTR ? a.g_ptr[1] : nullptr;
-  const T bval = a.g_val[1], bq = a.f_val[1];
-  const bool tiny_is_zero = a.f_val[1] >= (T)kTinyIsZeroRadius;     // device_math.hpp: norm2_leq0_fast
-  auto off_of = [&](idx_t c) { return ((unsigned)c * (unsigned)ny + (unsigned)row0) * (unsigned)sizeof(T); };
-  const unsigned lds_base = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)lds);
-  const unsigned lane_addr = lds_base + (unsigned)lane * 16u;
-  auto ring_issue = [&](idx_t k) {
-    if (active) {
-      const unsigned o = off_of(k);
-      char* slot = lds + lw_ring_slot(k) * kSlot;
-      __builtin_amdgcn_global_load_lds((glb_void_k*)(reinterpret_cast<const char*>(y) + o), (lds_void_k*)(slot), 16, 0, ITERK_LOAD_AUX);
-      __builtin_amdgcn_global_load_lds((glb_void_k*)(reinterpret_cast<const char*>(y2base) + o), (lds_void_k*)(slot + 1024), 16, 0, ITERK_LOAD_AUX);
-      __builtin_amdgcn_global_load_lds((glb_void_k*)(reinterpret_cast<const char*>(x) + o), (lds_void_k*)(slot + 2048), 16, 0, ITERK_LOAD_AUX);
-      if (BPTR) __builtin_amdgcn_global_load_lds((glb_void_k*)(reinterpret_cast<const char*>(bptr) + o), (lds_void_k*)(slot + 3072), 16, 0, ITERK_LOAD_AUX);
-    }
-  };
-  V4 n0 = {}, n1 = {}, n2 = {}, n3 = {};           // the column a step receives: y_1, y_2, x, b of the level below
-  auto column_read = [&](unsigned slot_off) {       // four ds_read_b128, waited for by column_wait
-    const unsigned addr = lane_addr + slot_off;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(n0) : "v"(addr) : "memory");
-    asm volatile("ds_read_b128 %0, %1 offset:1024" : "=v"(n1) : "v"(addr) : "memory");
-    asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(n2) : "v"(addr) : "memory");
-    if (BPTR) asm volatile("ds_read_b128 %0, %1 offset:3072" : "=v"(n3) : "v"(addr) : "memory");
-  };
-  auto column_wait = [&]() { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(n0), "+v"(n1), "+v"(n2), "+v"(n3)::"memory"); };
-  auto column_write = [&](unsigned slot_off, const T (&v0)[VEC], const T (&v1)[VEC], const T (&v2)[VEC], const T (&v3)[VEC]) {
-    const unsigned addr = lane_addr + slot_off;
-    V4 w0, w1, w2, w3;
-#pragma unroll
-    for (int j = 0; j < VEC; j++) { w0[j] = v0[j]; w1[j] = v1[j]; w2[j] = v2[j]; w3[j] = v3[j]; }
-    asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(w0) : "memory");
-    asm volatile("ds_write_b128 %0, %1 offset:1024" ::"v"(addr), "v"(w1) : "memory");
-    asm volatile("ds_write_b128 %0, %1 offset:2048" ::"v"(addr), "v"(w2) : "memory");
-    if (BPTR) asm volatile("ds_write_b128 %0, %1 offset:3072" ::"v"(addr), "v"(w3) : "memory");
-  };
-
-  // the state of ONE level: x^(l-1), y^(l-1), b and x^l at the columns p - 1 and p (which index holds which alternates: `stage`)
-  T XP[2][VEC], YP[2][2][VEC], BP[2][VEC], XN[2][VEC];
-#pragma unroll
-  for (int s = 0; s < 2; s++)
-#pragma unroll
-    for (int j = 0; j < VEC; j++) { XP[s][j] = 0; YP[s][0][j] = 0; YP[s][1][j] = 0; BP[s][j] = 0; XN[s][j] = 0; }
-
-  // primal step at column c: x^l = prox_g(x^(l-1) - tau T K^T y^(l-1)) -- the EXACT forms of `primal` above
-  auto primal = [&](auto inner, idx_t c, const T (&y1c)[VEC], const T (&y2c)[VEC], const T (&y1p)[VEC], const T (&xin)[VEC], const T (&bc)[VEC], T (&xn)[VEC]) {
-    constexpr bool I = decltype(inner)::value;
-    const T up = lane_up(y2c[VEC - 1]);            // lane 0: no source, its first row is halo
-    T parg[VEC];
-#pragma unroll
-    for (int j = 0; j < VEC; j++) {
-      const idx_t row = row0 + j;
-      const T upj = (j > 0) ? y2c[(j + VEC - 1) % VEC] : up;
-      const T divy = ((I || row < ny - 1) ? y2c[j] : (T)0) - ((I || row > 0) ? upj : (T)0);
-      const T divx = ((I || c < nx - 1) ? y1c[j] : (T)0) - ((I || c > 0) ? y1p[j] : (T)0);
-      const T sdiv = divx + divy;
-      const T kty = (T)0 - sdiv;
-      const T arg = xin[j] - P.tauT * kty;
-      parg[j] = arg - bc[j];
-    }
-    T r[VEC];
-    if (GFN == PROST_FN_SQUARE) div_to_float_exact_vec<VEC>(parg, P.sq, r);
-    else {
-#pragma unroll
-      for (int j = 0; j < VEC; j++) r[j] = f1d_apply<T, GFN>(GFN, parg[j], P.step, a.g_val[5], a.g_val[6]);
-    }
-#pragma unroll
-    for (int j = 0; j < VEC; j++) xn[j] = r[j] + bc[j];
-  };
-  // dual step at column c: y^l = prox_f*(y^(l-1) + sigma S K ((1 + theta) x^l - theta x^(l-1))) -- the EXACT forms of `dual` above
-  auto dual = [&](auto inner, idx_t c, const T (&xn_c)[VEC], const T (&xn_n)[VEC], const T (&xo_c)[VEC], const T (&xo_n)[VEC], const T (&y1c)[VEC],
-                  const T (&y2c)[VEC], T (&o1)[VEC], T (&o2)[VEC]) {
-    constexpr bool I = decltype(inner)::value;
-    const bool has_next = I || c + 1 < nx;
-    const T bel_n = lane_down(xn_c[0]);            // lane 63: no source, its last row is halo
-    const T bel_o = lane_down(xo_c[0]);
-    T av[2][VEC], nv[VEC], out[2][VEC];
-#pragma unroll
-    for (int j = 0; j < VEC; j++) {
-      const idx_t row = row0 + j;
-      const T below_n = (j < VEC - 1) ? xn_c[(j + 1) % VEC] : bel_n;
-      const T below_o = (j < VEC - 1) ? xo_c[(j + 1) % VEC] : bel_o;
-      const T kx1 = has_next ? xn_n[j] - xn_c[j] : (T)0;
-      const T kx2 = (I || row < ny - 1) ? below_n - xn_c[j] : (T)0;
-      const T kp1 = has_next ? xo_n[j] - xo_c[j] : (T)0;
-      const T kp2 = (I || row < ny - 1) ? below_o - xo_c[j] : (T)0;
-      const T arg1 = y1c[j] + P.sigS * (P.opt * kx1 - P.theta * kp1);
-      const T arg2 = y2c[j] + P.sigS * (P.opt * kx2 - P.theta * kp2);
-      T norm = 0;
-      norm += arg1 * arg1;
-      norm += arg2 * arg2;
-      av[0][j] = arg1; av[1][j] = arg2; nv[j] = norm;
-    }
-    norm2_leq0_fast<T, 2, VEC, true>(nv, av, bq, tiny_is_zero, out);
-#pragma unroll
-    for (int j = 0; j < VEC; j++) { o1[j] = out[0][j]; o2[j] = out[1][j]; }
-  };
-
-  // ---- prologue: zero the LDS (lanes outside the image never receive data, links before their first write), start the ring ----
-  if (lvl == 1 && active && xa - K >= 0) ldv_o<T, VEC, false>(y, off_of(xa - K), YP[1][0], VEC);      // y_1^0 at column xa - K: the left neighbour of P_1's first column
-  {
-    V4* z = reinterpret_cast<V4*>(lds);
-    const V4 zero = {};
-    for (int i = threadIdx.x; i < lw_lds_bytes(K, NB) / 16; i += K * kWave) z[i] = zero;
-  }
-  asm volatile("s_waitcnt vmcnt(0)" : "+v"(YP[1][0][0]), "+v"(YP[1][0][1]), "+v"(YP[1][0][2]), "+v"(YP[1][0][3])::"memory");
-  __syncthreads();
-  const idx_t p0 = lw_col(K, xa, 1, 0);
-  if (lvl == 1) {
-#pragma unroll
-    for (int r = 0; r < R - 1; r++) if (lw_loaded(K, xa, xb, nx, p0 + r)) ring_issue(p0 + r);
-  }
-  // every lane active and no lane on the first / last image row: the whole strip is interior
-  const bool strip_inner = (idx_t)strip * kLevelWaveRows - H * VEC >= 1 && (idx_t)strip * kLevelWaveRows + (idx_t)(kWave - H) * VEC < ny - 1;
-  const unsigned link_in = (unsigned)(R + 2 * (lvl - 2)) * kSlot, link_out = (unsigned)(R + 2 * (lvl - 1)) * kSlot;      // (wave 1 has no link_in, wave K no link_out)
-
-  // nw: the index the state arrays keep column p at in this step, 1 - nw: column p - 1.  The two alternate from step to step (the loop
-  // below is unrolled by two), so no register is copied to shift the pipeline by a column.
-  auto stage = [&](auto inner, auto parity, idx_t p) {
-    constexpr int nw = decltype(parity)::value, od = 1 - nw;
-    const idx_t q = p - 1;
-    if (lw_p_active(K, xa, xb, nx, lvl, p)) primal(inner, p, YP[nw][0], YP[nw][1], YP[od][0], XP[nw], BP[nw], XN[nw]);
-    else {          // (as if the pipeline had shifted: the column keeps the value of the one before it)
-#pragma unroll
-      for (int j = 0; j < VEC; j++) XN[nw][j] = XN[od][j];
-    }
-    if (lvl == K && owner && lw_stores_x(xa, xb, p)) stv_o<T, VEC, ITERK_NT, false>(x_out, off_of(p), XN[nw], VEC);
-    T o1[VEC] = {}, o2[VEC] = {};
-    if (lw_d_active(K, xa, xb, nx, lvl, q)) {
-      dual(inner, q, XN[od], XN[nw], XP[od], XP[nw], YP[od][0], YP[od][1], o1, o2);
-      if (lvl == K && owner && lw_stores_y(xa, xb, q)) { stv_o<T, VEC, ITERK_NT, false>(y_out, off_of(q), o1, VEC); stv_o<T, VEC, ITERK_NT, false>(y2out, off_of(q), o2, VEC); }
-    }
-    if (lvl < K) column_write(link_out + (unsigned)nw * kSlot, o1, o2, XN[od], BP[od]);      // column q of level lvl into slot lw_slot_written(t)
-  };
-  auto step = [&](auto parity, int t) {
-    constexpr int nw = decltype(parity)::value;
-    static_assert(lw_slot_written(nw) == nw && lw_slot_read(nw) == 1 - nw, "the link slot of a step is its parity");
-    const idx_t p = lw_col(K, xa, lvl, t);
-    n0 = V4{}; n1 = V4{}; n2 = V4{}; n3 = V4{};
-    if (lvl == 1) {
-      // the batch of column p + R - 1 goes into the slot of column p - 1, read (and waited for) in the previous step
-      if (lw_loaded(K, xa, xb, nx, p + R - 1)) ring_issue(p + R - 1);
-      if (lw_loaded(K, xa, xb, nx, p)) {
-        // batches issued behind column p's: those of p + 1 .. p + R - 1 that exist (the loaded columns are one range)
-        static_assert(R == 3, "the counted waits below are written for three slots");
-        if (lw_loaded(K, xa, xb, nx, p + 2)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NB) : "memory");
-        else if (lw_loaded(K, xa, xb, nx, p + 1)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NB) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        column_read((unsigned)lw_ring_slot(p) * kSlot);
-      }
-    } else if (t >= 1) {
-      column_read(link_in + (unsigned)(1 - nw) * kSlot);
-    }
-    column_wait();
-#pragma unroll
-    for (int j = 0; j < VEC; j++) { YP[nw][0][j] = n0[j]; YP[nw][1][j] = n1[j]; XP[nw][j] = n2[j]; BP[nw][j] = BPTR ? n3[j] : bval; }
-    // every stencil of both stages strictly inside the image: the select-free instance
-    if (strip_inner && p >= 2 && p < nx - 1) stage(std::true_type(), parity, p);
-    else stage(std::false_type(), parity, p);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  };
-  const int steps = lw_steps(K, xa, xb);
-  for (int t = 0; t < steps; t += 2) {
-    step(int_c<0>(), t);
-    if (t + 1 < steps) step(int_c<1>(), t + 1);
-  }
-  if constexpr (PLACE) {          // HW_ID[15:0]: wave, SIMD, pipe, CU, SH, SE; XCC_ID[3:0] above them
-    const unsigned hw = __builtin_amdgcn_s_getreg((16 - 1) << 11 | 4), xcc = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20);
-    if (lane == 0) place[(size_t)blockIdx.x * K + (lvl - 1)] = hw | xcc << 16;
-  }
-}
-
 // ---- host side ------------------------------------------------------------------------------------------------------------
 static bool iterk_shape_ok(const prost_hip_fused_desc* d, int dtype) {
   if (!d || dtype != 0 || (d->arith != PROST_HIP_ARITH_FMAD && d->arith != PROST_HIP_ARITH_EXACT)) return false;
@@ -706,23 +450,10 @@ static int run_iterk(const prost_hip_fused_desc* d, float* x_out, float* y_out, 
   const PdhgRecord<float>* rec = static_cast<const PdhgRecord<float>*>(record);
   if constexpr (K == 3 || K == 4) {
     if (iterk_levelwave(d, K, out4 != nullptr)) {
-      const dim3 blockw(K * kWave);
       const bool bpw = d->g_coeff_ptr[1] != nullptr;
       unsigned* const place = iterk_place_record(ws);
       if (place && !(K == 4 && d->g_fn == PROST_FN_SQUARE && bpw)) { set_error("fused K-iteration launch: the placement record exists for K = 4, square, per-pixel b"); return 1; }
-#define GOW(G, BP) PH_LAUNCH((fused_iter2d_xkw_kernel<K, G, BP>), grid, blockw, 0, s, x_out, y_out, x, y, a, sp, rec, nullptr)
-      if constexpr (K == 4) {
-        if (place) {
-          PH_LAUNCH((fused_iter2d_xkw_kernel<4, PROST_FN_SQUARE, true, true>), grid, blockw, 0, s, x_out, y_out, x, y, a, sp, rec, place);
-          hipError_t e_ = hipGetLastError();
-          return e_ != hipSuccess ? fail(e_, "fused K-iteration kernel (level per wavefront, placement record)") : 0;
-        }
-      }
-      if (d->g_fn == PROST_FN_SQUARE) { if (bpw) GOW(PROST_FN_SQUARE, true); else GOW(PROST_FN_SQUARE, false); }
-      else { if (bpw) GOW(PROST_FN_ABS, true); else GOW(PROST_FN_ABS, false); }
-#undef GOW
-      { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return fail(e_, "fused K-iteration kernel (level per wavefront)"); }
-      return 0;
+      return launch_iterk_levelwave<K>(d->g_fn, bpw, grid, s, x_out, y_out, x, y, a, sp, rec, place);
     }
   }
   constexpr int R = IterKGeom<K>::R, W = IterKGeom<K>::W;
