@@ -10,6 +10,7 @@
 #include "prost/linop/radon2d.hpp"
 #include "prost/linop/sample2d.hpp"
 #include "prost/linop/sym_gradient2d.hpp"
+#include "prost/linop/tensor_gradient2d.hpp"
 #include "prost/linop/wavelet2d.hpp"
 
 namespace prost {
@@ -419,6 +420,36 @@ class BlockSymGradient2D : public ProductBlock<T> {
   double WeightPower(T alpha) const { return sym_gradient2d::WeightPower((double)sym_gradient2d::RoundWeight<T>(w_), (double)alpha); }
   size_t nx_, ny_, L_;
   double w_;               ///< as given; the kernels and the sums round it to T once
+};
+
+/// K = T grad on L channels of an ny x nx grid, without a matrix: the gradient weighted per pixel by a scalar (mode 1, edge-weighted TV),
+/// by one weight per axis (mode 2) or by a symmetric 2 x 2 tensor (mode 3, the diffusion tensor of anisotropic Huber-L1 and TGV).  2 L N
+/// rows (gx, gy planes, the range layout of gradient2d) by L N columns.  Arithmetic, sums and error bound:
+/// prost/linop/tensor_gradient2d.hpp.  No describe(): the block runs on the generic paths.  Stored on the device: the `mode` planes of
+/// the tensor, N values each, shared by all channels.
+template <typename T>
+class BlockTensorGradient2D : public ProductBlock<T> {
+ public:
+  /// checks every argument (messages start with "BlockTensorGradient2D: "); tensor: mode planes of nx ny values one after the other;
+  /// declared_rows / declared_cols < 0: no size was declared
+  static BlockTensorGradient2D<T>* Create(size_t row, size_t col, double nx, double ny, double L, double mode, const std::vector<double>& tensor,
+                                          double declared_rows = -1, double declared_cols = -1);
+  virtual void Initialize();
+  virtual void Release();
+  virtual T row_sum(size_t row, T alpha) const;
+  virtual T col_sum(size_t col, T alpha) const;
+  virtual void row_sums(T* out, T alpha) const;              ///< one pass over the pixels
+  virtual void col_sums(T* out, T alpha) const;
+  virtual size_t gpu_mem_amount() const { return tensor_.size() * sizeof(T); }
+
+ protected:
+  BlockTensorGradient2D(size_t row, size_t col, size_t nx, size_t ny, size_t L, int mode)
+      : ProductBlock<T>(row, col, 2 * L * nx * ny, L * nx * ny), nx_(nx), ny_(ny), L_(L), mode_(mode) {}
+  virtual void Product(T* res, const T* rhs, bool transpose, bool accumulate);
+  size_t nx_, ny_, L_;
+  int mode_;
+  std::vector<T> tensor_;          ///< rounded once to T
+  device_vector<T> d_tensor_;
 };
 
 /// constant-coefficient multi-diagonal block; `identity` maps here (block_diags.hpp, identity.m:11-12)

@@ -384,6 +384,23 @@ int prost_hip_wavelet2d_f64(const prost_hip_wavelet2d_geometry* geometry, const 
  * or L of 0, w not finite, w zero after rounding to T, null pointers, 3 L N beyond 2^53. */
 int prost_hip_linop_sym_gradient2d_f32(float* res, const float* rhs, size_t nx, size_t ny, size_t L, double w, int transpose, int accumulate, void* stream);
 int prost_hip_linop_sym_gradient2d_f64(double* res, const double* rhs, size_t nx, size_t ny, size_t L, double w, int transpose, int accumulate, void* stream);
+/* BlockTensorGradient2D (additions; ABI version unchanged; kernels_linop_tensor_gradient2d.hip, arithmetic and order of operations:
+ * prost/linop/tensor_gradient2d.hpp): K = T grad on L channels of an ny x nx grid, N = nx ny, pixel (y, x) at p = y + x ny.  Domain,
+ * L N values: u_c[p] at c N + p.  Range, 2 L N values: gx_c[p] at c N + p, gy_c[p] at (L + c) N + p (the range layout of gradient2d).
+ * tensor: a DEVICE pointer to `mode` planes of N values shared by all channels -- mode 1: g (T = g I); 2: a, c (T = diag(a, c));
+ * 3: a, b, c (T = [[a, b], [b, c]]).  With ax = [x < nx-1], bx = [x > 0], ay = [y < ny-1], by = [y > 0], every difference, product and
+ * addition rounded once, a masked term selected away (never multiplied by zero) and a term the mode lacks never formed:
+ *   transpose == 0:  dx = u[p+ny] - u[p], dy = u[p+1] - u[p];   mode 1: gx = (ax) g dx, gy = (ay) g dy;   2: gx = (ax) a dx, gy = (ay) c dy;
+ *                    3: gx = (ax) a dx + (ay) b dy, gy = (ax) b dx + (ay) c dy
+ *   transpose != 0:  qx = a gx + b gy, qy = b gx + c gy at p (mode 1: g gx, g gy; 2: a gx, c gy);  divx = (ax) qx[p], (bx) -= qx[p-ny];
+ *                    divy = (ay) qy[p], (by) -= qy[p-1];  res = 0 - (divx + divy)        (accumulate: res - (divx + divy))
+ * accumulate != 0 stores res + value in the forward product.  Mode 1 with g = 1 gives the bits of prost_hip_grad2d_fwd / _adj.  Any
+ * alignment of T is accepted (16-byte aligned res, rhs and tensor and a height that is a multiple of 16 / sizeof(T) take the vector
+ * kernels; the bits are the same).  Aliasing: res must NOT overlap rhs or the tensor.  No atomics: a call repeats its bits.  No
+ * allocation, copy or synchronisation.  Refused without a launch: nx, ny or L of 0, a mode outside 1 .. 3, null pointers, 2 L N beyond
+ * 2^53.  The values of the tensor are the caller's: BlockTensorGradient2D refuses non-finite ones before it uploads them. */
+int prost_hip_linop_tensor_gradient2d_f32(float* res, const float* rhs, const float* tensor, size_t nx, size_t ny, size_t L, int mode, int transpose, int accumulate, void* stream);
+int prost_hip_linop_tensor_gradient2d_f64(double* res, const double* rhs, const double* tensor, size_t nx, size_t ny, size_t L, int mode, int transpose, int accumulate, void* stream);
 /* x = beta * x (beta == 0 -> zero fill): thrust::fill / transform at linearoperator.cu:140-147 */
 /* x[i] = value (thrust::fill, linearoperator.cu:140-147; also used for preconditioners that are one constant: the
  * gradient blocks' row / column sums are, block_gradient2d.cu:154-163, so nothing is uploaded for them) */

@@ -472,6 +472,74 @@ def sym_gradient2d(nx, ny, L=1, w=math.sqrt(0.5)):
     return lambda row, col, nrows, ncols: [["sym_gradient2d", row, col, data], sz]
 
 
+TENSOR_GRADIENT2D_MAX_SIZE = 2 ** 53       # sizes travel as doubles
+
+
+def tensor_gradient2d(nx, ny, L, tensor):
+    """K = T grad on L channels of an ny x nx grid, applied without a matrix: the gradient weighted per pixel by a scalar (edge-weighted
+    TV, g |grad u| with g = exp(-beta |grad f|^gamma)), by one weight per axis, or by a symmetric 2 x 2 tensor (the image-driven diffusion
+    tensor D^(1/2) of anisotropic Huber-L1 stereo / flow and anisotropic TGV).  N = nx ny, pixel (y, x) at p = y + x ny.  Domain, L N
+    values: u_c[p] at c N + p.  Range, 2 L N values, the range layout of gradient2d(nx, ny, L): gx_c[p] at c N + p, gy_c[p] at
+    (L + c) N + p, so sum_norm2(2 L, False, ..) or sum_norm2(2, False, ..) group as they do behind gradient2d.  The tensor is one
+    field shared by all channels, k planes of N values, each rounded once to the precision of the problem:
+        k = 1  g        gx = g dx,         gy = g dy
+        k = 2  a, c     gx = a dx,         gy = c dy
+        k = 3  a, b, c  gx = a dx + b dy,  gy = b dx + c dy
+    with dx, dy the forward differences of gradient2d (zero in the last column / row).  tensor: a (k, N) array, a (k, ny, nx) array
+    t[i, y, x] (each plane is flattened with y fastest), a vector of N values (k = 1), or a sequence of k planes, each a vector of N
+    values or an (ny, nx) array.  Zeros are legal (an edge that is switched off); non-finite values are refused.  With g = 1 the block is
+    gradient2d bit for bit.  The device stores the k N values of the tensor and nothing per channel; the sparse matrix of the same
+    operator stores 4 (k = 1, 2) or 6 (k = 3) entries with their indices per pixel and channel, once for each side."""
+    for name, v in (("nx", nx), ("ny", ny), ("L", L)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or int(v) != v:
+            raise ValueError("tensor_gradient2d: %s = %r is not an integer" % (name, v))
+        if v < 1:
+            raise ValueError("tensor_gradient2d: %s = %r has to be at least 1" % (name, v))
+    nx, ny, L = int(nx), int(ny), int(L)
+    N = nx * ny
+    if 2 * L * N > TENSOR_GRADIENT2D_MAX_SIZE:
+        raise ValueError("tensor_gradient2d: 2 L nx ny = %d rows; the size has to stay within 2^53" % (2 * L * N))
+
+    def numbers(v, what):
+        try:
+            if np.asarray(v).dtype.kind not in "iuf":
+                raise TypeError
+            return np.array(v, dtype=np.float64, copy=True)
+        except (TypeError, ValueError):
+            raise ValueError("tensor_gradient2d: %s has to be an array of numbers" % what)
+
+    def plane(v, what):
+        v = numbers(v, what)
+        if v.ndim == 2 and v.shape == (ny, nx):
+            v = v.reshape(-1, order="F")                   # p = y + x ny
+        if v.ndim != 1 or v.size != N:
+            raise ValueError("tensor_gradient2d: %s has shape %r; a plane is a vector of nx ny = %d values or an (ny, nx) = (%d, %d) array"
+                             % (what, v.shape, N, ny, nx))
+        return v
+
+    if isinstance(tensor, (list, tuple)) and len(tensor) > 0 and not np.isscalar(tensor[0]):
+        planes = [plane(v, "plane %d of the tensor" % i) for i, v in enumerate(tensor)]
+    else:
+        t = numbers(tensor, "the tensor")
+        if t.ndim == 1:
+            planes = [plane(t, "the tensor")]
+        elif t.ndim == 2:
+            planes = [plane(v, "plane %d of the tensor" % i) for i, v in enumerate(t)]
+        elif t.ndim == 3:
+            planes = [plane(v, "plane %d of the tensor" % i) for i, v in enumerate(t)]
+        else:
+            raise ValueError("tensor_gradient2d: the tensor has shape %r; it is a (k, N) or (k, ny, nx) array or a sequence of k planes" % (t.shape,))
+    k = len(planes)
+    if k not in (1, 2, 3):
+        raise ValueError("tensor_gradient2d: the tensor has k = %d planes; k has to be 1 (scalar), 2 (per axis) or 3 (symmetric tensor)" % k)
+    flat = np.concatenate(planes)
+    if not np.isfinite(flat).all():
+        raise ValueError("tensor_gradient2d: the tensor holds a non-finite value")
+    sz = [2 * L * N, L * N]
+    data = [nx, ny, L, k, flat]
+    return lambda row, col, nrows, ncols: [["tensor_gradient2d", row, col, data], sz]
+
+
 def diags(nrows, ncols, factors, offsets):
     sz = [nrows, ncols]
     data = [nrows, ncols, np.atleast_1d(np.asarray(factors, dtype=np.float64)),

@@ -509,6 +509,16 @@ std::map<std::string, typename Factory<T>::BlockFactory>& Factory<T>::block_reg(
       return BlockSymGradient2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), GetScalarFromCell(d, 3), size.first,
                                            size.second);
     };
+    // K = T grad without a matrix: cells { nx, ny, L, k, tensor (full vector: k planes of nx ny values one after the other) }; a caller
+    // that also knows the size it means the block to have appends { nrows, ncols } and gets it checked.  Every argument check is
+    // BlockTensorGradient2D<T>::Create's.
+    reg["tensor_gradient2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
+      const auto size = declared_size(d, 5, "BlockTensorGradient2D: the data cells are { nx, ny, L, k, tensor } or { nx, ny, L, k, tensor, nrows, ncols }.");
+      const prost_value* pt = d->cells[4];
+      if (!pt || pt->kind != PROST_VALUE_MATRIX) throw Exception("BlockTensorGradient2D: the tensor has to be a full vector of type single or double.");
+      return BlockTensorGradient2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), GetScalarFromCell(d, 3),
+                                              std::vector<double>(pt->data.begin(), pt->data.begin() + pt->rows * pt->cols), size.first, size.second);
+    };
     // the dense blocks (factory.cpp:590-601, :694-716): cell 0 is a full matrix, column-major, converted to T.  A sparse cell is refused:
     // the reference would read its value array as if it were the full matrix.
     auto dense_data = [](const prost_value* pm) {

@@ -1016,6 +1016,58 @@ void BlockSymGradient2D<T>::Product(T* r, const T* x, bool transpose, bool acc) 
 template class BlockSymGradient2D<float>;
 template class BlockSymGradient2D<double>;
 
+// ---- K = T grad: the gradient weighted by a per-pixel scalar, axis weights or symmetric tensor, without a matrix ----
+template <typename T>
+BlockTensorGradient2D<T>* BlockTensorGradient2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, double mode, const std::vector<double>& tensor,
+                                                           double declared_rows, double declared_cols) {
+  std::stringstream ss;
+  ss << "BlockTensorGradient2D: ";
+  const double kMaxSize = 9007199254740992.0;      // 2^53: sizes travel as doubles
+  for (const auto& v : {std::make_pair("nx", nx), std::make_pair("ny", ny), std::make_pair("L", L)})
+    if (!(v.second >= 1) || v.second != std::floor(v.second) || v.second > kMaxSize) {
+      ss << v.first << " = " << v.second << " has to be a positive integer."; throw Exception(ss.str());
+    }
+  if (!(mode == 1 || mode == 2 || mode == 3)) { ss << "the tensor has k = " << mode << " planes; k has to be 1 (scalar), 2 (per axis) or 3 (symmetric tensor)."; throw Exception(ss.str()); }
+  const double rows = 2 * L * nx * ny, cols = L * nx * ny;
+  if (!(2 * L * (nx * ny) <= kMaxSize) || !(nx * ny <= kMaxSize)) { ss << "2 L nx ny = " << rows << " rows; the size has to stay within 2^53."; throw Exception(ss.str()); }
+  if ((double)tensor.size() != mode * nx * ny) {
+    ss << "the tensor holds " << tensor.size() << " values, not k = " << mode << " planes of nx ny = " << nx * ny << "."; throw Exception(ss.str());
+  }
+  if ((declared_rows >= 0 || declared_cols >= 0) && (declared_rows != rows || declared_cols != cols)) {
+    ss << "the declared size " << declared_rows << " x " << declared_cols << " is not 2 L nx ny x L nx ny = " << rows << " x " << cols << "."; throw Exception(ss.str());
+  }
+  std::unique_ptr<BlockTensorGradient2D<T>> b(new BlockTensorGradient2D<T>(row, col, (size_t)nx, (size_t)ny, (size_t)L, (int)mode));
+  b->tensor_.resize(tensor.size());
+  for (size_t i = 0; i < tensor.size(); i++) {
+    const T t = (T)tensor[i];                       // rounded once
+    if (!std::isfinite((double)t)) {
+      ss << "value " << i % (size_t)(nx * ny) << " of plane " << i / (size_t)(nx * ny) << " of the tensor, " << tensor[i] << ", is not finite"
+         << (std::is_same<T, float>::value ? " in single precision." : "."); throw Exception(ss.str());
+    }
+    b->tensor_[i] = t;
+  }
+  return b.release();
+}
+template <typename T>
+void BlockTensorGradient2D<T>::Initialize() { d_tensor_ = tensor_; }
+template <typename T>
+void BlockTensorGradient2D<T>::Release() { d_tensor_.clear(); }
+template <typename T>
+T BlockTensorGradient2D<T>::row_sum(size_t row, T alpha) const { return (T)tensor_gradient2d::RowSum(row, tensor_.data(), nx_, ny_, L_, mode_, (double)alpha); }
+template <typename T>
+T BlockTensorGradient2D<T>::col_sum(size_t col, T alpha) const { return (T)tensor_gradient2d::ColSum(col, tensor_.data(), nx_, ny_, L_, mode_, (double)alpha); }
+template <typename T>
+void BlockTensorGradient2D<T>::row_sums(T* out, T alpha) const { tensor_gradient2d::RowSums<T>(out, tensor_.data(), nx_, ny_, L_, mode_, (double)alpha); }
+template <typename T>
+void BlockTensorGradient2D<T>::col_sums(T* out, T alpha) const { tensor_gradient2d::ColSums<T>(out, tensor_.data(), nx_, ny_, L_, mode_, (double)alpha); }
+template <typename T>
+void BlockTensorGradient2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
+  if (d_tensor_.size() != tensor_.size()) throw Exception("BlockTensorGradient2D used before Initialize().");
+  CheckHip(Api<T>::linop_tensor_gradient2d(r, x, d_tensor_.data(), nx_, ny_, L_, mode_, transpose ? 1 : 0, acc ? 1 : 0, CurrentStream()), "linop_tensor_gradient2d");
+}
+template class BlockTensorGradient2D<float>;
+template class BlockTensorGradient2D<double>;
+
 // ---- diags block ----
 static bool g_diags_quirk = false;
 template <typename T> void BlockDiags<T>::SetReferenceGridQuirk(bool on) { g_diags_quirk = on; }
