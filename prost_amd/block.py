@@ -83,6 +83,37 @@ def id_kron_dense(K, diaglength):
     return _kron_dense("id_kron_dense", K, diaglength)
 
 
+_NUMBER = (int, float, np.integer, np.floating)
+
+
+def _whole(block, name, v, loose=False):
+    """v, a Python or numpy number with an integer value, as an int.  loose: the three oldest builders (dataterm_sublabel, conv2d,
+    conv2d_strided) take whatever numpy can test, a 0-d array for instance, and let numpy's TypeError for anything else escape."""
+    if isinstance(v, bool) or not (loose or isinstance(v, _NUMBER)) or not np.isfinite(v) or int(v) != v:
+        raise ValueError("%s: %s = %r is not an integer" % (block, name, v))
+    return int(v)
+
+
+def _integer(block, name, v, top=None, loose=False):
+    """_whole, and 1 <= v (<= top)"""
+    n = _whole(block, name, v, loose)
+    if v < 1:
+        raise ValueError("%s: %s = %r has to be at least 1" % (block, name, v))
+    if top is not None and v > top:
+        raise ValueError("%s: %s = %r has to be at most %d" % (block, name, v, top))
+    return n
+
+
+def _numbers(block, v, refusal):
+    """v, an array of integers or floats, as a new float64 array"""
+    try:
+        if np.asarray(v).dtype.kind not in "iuf":
+            raise TypeError
+        return np.array(v, dtype=np.float64, copy=True)
+    except (TypeError, ValueError):
+        raise ValueError("%s: %s" % (block, refusal))
+
+
 def dataterm_sublabel(nx, ny, L, left, right):
     """The coupling of the sublabel-accurate data term (Moellenhoff et al., CVPR 2016) for L equidistant labels on [left, right],
     applied without a matrix.  k = L - 1 intervals, N = nx ny pixels, every part k planes of N values (element (p, i) at i N + p, the
@@ -90,10 +121,8 @@ def dataterm_sublabel(nx, ny, L, left, right):
     labelling and the interval weights; range [r ; s]: (r_i, s_i) lives in the epigraph of the conjugate of piece i
     (alpha = left + i delta, beta = alpha + delta, delta = (right - left) / (L - 1)).  Per pixel
     r_i = delta u_i + gamma_i w_i - delta sum_{j > i} w_j and s_i = -w_i."""
-    for name, v in (("nx", nx), ("ny", ny), ("L", L)):
-        if isinstance(v, bool) or not np.isfinite(v) or int(v) != v:
-            raise ValueError("dataterm_sublabel: %s = %r is not an integer" % (name, v))
-    nx, ny, L, left, right = int(nx), int(ny), int(L), float(left), float(right)
+    nx, ny, L = [_whole("dataterm_sublabel", name, v, loose=True) for name, v in (("nx", nx), ("ny", ny), ("L", L))]
+    left, right = float(left), float(right)
     if L < 2:
         raise ValueError("dataterm_sublabel: L = %d labels, at least 2 are needed" % L)
     if nx < 1 or ny < 1:
@@ -122,28 +151,30 @@ def conv2d_size(nx, ny, ky, kx, shape):
     raise ValueError("conv2d: unknown shape %r (full, same or valid)" % (shape,))
 
 
+def _conv_window(block, kernel):
+    """the window of conv2d and conv2d_strided as a new column-major float64 matrix"""
+    kernel = np.array(kernel, dtype=np.float64, order="F", copy=True)
+    if kernel.ndim != 2 or kernel.size == 0:
+        raise ValueError("%s: the window has to be a non-empty matrix (2-D), got shape %r" % (block, kernel.shape))
+    ky, kx = kernel.shape
+    if ky > CONV2D_MAX_WINDOW or kx > CONV2D_MAX_WINDOW:
+        raise ValueError("%s: the window is %d x %d, windows up to %d x %d are supported" % (block, ky, kx, CONV2D_MAX_WINDOW, CONV2D_MAX_WINDOW))
+    if not np.isfinite(kernel).all():
+        raise ValueError("%s: the window holds a non-finite value" % block)
+    if not kernel.any():
+        raise ValueError("%s: the window has no non-zero tap" % block)
+    return kernel
+
+
 def conv2d(nx, ny, L, kernel, shape="full"):
     """2-D convolution of L column-major image planes of ny x nx (element (y, x, c) at y + x ny + c nx ny, the layout of
     gradient2d(nx, ny, L)) with one ky x kx window, zero padding, applied without a matrix:
     out(y, x) = sum_{i, j} kernel[i, j] in(y + oy - i, x + ox - j).  shape "full": (ny + ky - 1) x (nx + kx - 1) outputs per plane, the
     matrix kron(eye(L), convmtx2(kernel, ny, nx)); "same": ny x nx, MATLAB's conv2(.., 'same'); "valid": (ny - ky + 1) x (nx - kx + 1).
     Windows up to 31 x 31."""
-    for name, v in (("nx", nx), ("ny", ny), ("L", L)):
-        if isinstance(v, bool) or not np.isfinite(v) or int(v) != v:
-            raise ValueError("conv2d: %s = %r is not an integer" % (name, v))
-        if v < 1:
-            raise ValueError("conv2d: %s = %r has to be at least 1" % (name, v))
-    nx, ny, L = int(nx), int(ny), int(L)
-    kernel = np.array(kernel, dtype=np.float64, order="F", copy=True)
-    if kernel.ndim != 2 or kernel.size == 0:
-        raise ValueError("conv2d: the window has to be a non-empty matrix (2-D), got shape %r" % (kernel.shape,))
+    nx, ny, L = [_integer("conv2d", name, v, loose=True) for name, v in (("nx", nx), ("ny", ny), ("L", L))]
+    kernel = _conv_window("conv2d", kernel)
     ky, kx = kernel.shape
-    if ky > CONV2D_MAX_WINDOW or kx > CONV2D_MAX_WINDOW:
-        raise ValueError("conv2d: the window is %d x %d, windows up to %d x %d are supported" % (ky, kx, CONV2D_MAX_WINDOW, CONV2D_MAX_WINDOW))
-    if not np.isfinite(kernel).all():
-        raise ValueError("conv2d: the window holds a non-finite value")
-    if not kernel.any():
-        raise ValueError("conv2d: the window has no non-zero tap")
     if not isinstance(shape, str):
         raise ValueError("conv2d: unknown shape %r (full, same or valid)" % (shape,))
     (my, mx), _ = conv2d_size(nx, ny, ky, kx, shape)
@@ -161,7 +192,7 @@ CONV2D_STRIDED_MAX_STRIDE = 4
 
 def _pair(name, v, what):
     """an int or a pair (y, x) of ints -> (y, x)"""
-    vs = (v, v) if isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) else v
+    vs = (v, v) if isinstance(v, _NUMBER) and not isinstance(v, bool) else v
     try:
         vs = tuple(vs)
     except TypeError:
@@ -169,7 +200,7 @@ def _pair(name, v, what):
     if len(vs) != 2:
         raise ValueError("%s: the %s %r has to be an integer or a pair (y, x)" % (name, what, v))
     for e in vs:
-        if isinstance(e, bool) or not isinstance(e, (int, float, np.integer, np.floating)) or not np.isfinite(e) or int(e) != e:
+        if isinstance(e, bool) or not isinstance(e, _NUMBER) or not np.isfinite(e) or int(e) != e:
             raise ValueError("%s: the %s %r is not an integer" % (name, what, v))
     return int(vs[0]), int(vs[1])
 
@@ -191,22 +222,9 @@ def conv2d_strided(nx, ny, L, kernel, stride, shape="same", phase=(0, 0)):
     0 <= py < min(sy, cy), 0 <= px < min(sx, cx).  out(y, x) = sum_{i, j} kernel[i, j] in(y sy + py + oy - i, x sx + px + ox - j),
     my x mx = conv2d_strided_size(..) outputs per plane: the rows (y sy + py, x sx + px) of conv2d's matrix.  The adjoint is the
     fractionally strided ("transposed") convolution."""
-    for name, v in (("nx", nx), ("ny", ny), ("L", L)):
-        if isinstance(v, bool) or not np.isfinite(v) or int(v) != v:
-            raise ValueError("conv2d_strided: %s = %r is not an integer" % (name, v))
-        if v < 1:
-            raise ValueError("conv2d_strided: %s = %r has to be at least 1" % (name, v))
-    nx, ny, L = int(nx), int(ny), int(L)
-    kernel = np.array(kernel, dtype=np.float64, order="F", copy=True)
-    if kernel.ndim != 2 or kernel.size == 0:
-        raise ValueError("conv2d_strided: the window has to be a non-empty matrix (2-D), got shape %r" % (kernel.shape,))
+    nx, ny, L = [_integer("conv2d_strided", name, v, loose=True) for name, v in (("nx", nx), ("ny", ny), ("L", L))]
+    kernel = _conv_window("conv2d_strided", kernel)
     ky, kx = kernel.shape
-    if ky > CONV2D_MAX_WINDOW or kx > CONV2D_MAX_WINDOW:
-        raise ValueError("conv2d_strided: the window is %d x %d, windows up to %d x %d are supported" % (ky, kx, CONV2D_MAX_WINDOW, CONV2D_MAX_WINDOW))
-    if not np.isfinite(kernel).all():
-        raise ValueError("conv2d_strided: the window holds a non-finite value")
-    if not kernel.any():
-        raise ValueError("conv2d_strided: the window has no non-zero tap")
     if not isinstance(shape, str) or shape not in ("full", "same", "valid"):
         raise ValueError("conv2d_strided: unknown shape %r (full, same or valid)" % (shape,))
     (sy, sx), (py, px) = _pair("conv2d_strided", stride, "stride"), _pair("conv2d_strided", phase, "phase")
@@ -234,7 +252,7 @@ RADON2D_MAX_ANGLES = 4096
 
 
 def _radon2d_number(name, v):
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+    if isinstance(v, bool) or not isinstance(v, _NUMBER):
         raise ValueError("radon2d: %s = %r is not a number" % (name, v))
     return float(v)
 
@@ -252,16 +270,10 @@ def radon2d(nx, ny, L, angles, ndet=None, spacing=1.0, shift=0.0):
     ndet: None for radon2d_ndet(nx, ny, spacing); 0.5 <= spacing <= 8.  Per angle the ray is marched over the rows if
     |cos| >= |sin| and over the columns otherwise, and interpolated linearly along the other axis; a matrix entry is the
     interpolation weight times 1 / max(|cos|, |sin|).  Only five numbers per angle are stored."""
-    for name, v, top in (("nx", nx, RADON2D_MAX_SIDE), ("ny", ny, RADON2D_MAX_SIDE), ("L", L, None), ("ndet", ndet, None)):
-        if name == "ndet" and v is None:
-            continue
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or int(v) != v:
-            raise ValueError("radon2d: %s = %r is not an integer" % (name, v))
-        if v < 1:
-            raise ValueError("radon2d: %s = %r has to be at least 1" % (name, v))
-        if top is not None and v > top:
-            raise ValueError("radon2d: %s = %r has to be at most %d" % (name, v, top))
-    nx, ny, L = int(nx), int(ny), int(L)
+    nx, ny = _integer("radon2d", "nx", nx, RADON2D_MAX_SIDE), _integer("radon2d", "ny", ny, RADON2D_MAX_SIDE)
+    L = _integer("radon2d", "L", L)
+    if ndet is not None:
+        ndet = _integer("radon2d", "ndet", ndet)
     try:
         angles = np.array(angles, dtype=np.float64, copy=True)
     except (TypeError, ValueError):
@@ -279,7 +291,8 @@ def radon2d(nx, ny, L, angles, ndet=None, spacing=1.0, shift=0.0):
         raise ValueError("radon2d: spacing = %r has to be from 0.5 to 8" % (spacing,))
     if not np.isfinite(shift):
         raise ValueError("radon2d: shift = %r has to be finite" % (shift,))
-    ndet = radon2d_ndet(nx, ny, spacing) if ndet is None else int(ndet)
+    if ndet is None:
+        ndet = radon2d_ndet(nx, ny, spacing)
     if ndet > 2 ** 31 - 1025:
         raise ValueError("radon2d: ndet = %d has to be below 2^31 - 1024" % ndet)
     if ndet * angles.size >= 2 ** 31:
@@ -301,22 +314,11 @@ def sample2d(nx, ny, L, x, y):
     (dx, dy) is x = X + dx, y = Y + dy with X, Y the pixel grid in column-major order and M = nx ny.  The device stores the 2 M
     positions, M int32 sample indices sorted by cell and (ny + 1)(nx + 1) + 1 int32 cell offsets: about a quarter of the two sides of
     the sparse matrix.  Many samples inside one cell are correct but slow in the transpose."""
-    for name, v, top in (("nx", nx, SAMPLE2D_MAX_SIDE), ("ny", ny, SAMPLE2D_MAX_SIDE), ("L", L, None)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or int(v) != v:
-            raise ValueError("sample2d: %s = %r is not an integer" % (name, v))
-        if v < 1:
-            raise ValueError("sample2d: %s = %r has to be at least 1" % (name, v))
-        if top is not None and v > top:
-            raise ValueError("sample2d: %s = %r has to be at most %d" % (name, v, top))
-    nx, ny, L = int(nx), int(ny), int(L)
+    nx, ny = _integer("sample2d", "nx", nx, SAMPLE2D_MAX_SIDE), _integer("sample2d", "ny", ny, SAMPLE2D_MAX_SIDE)
+    L = _integer("sample2d", "L", L)
     pos = []
     for name, v in (("x", x), ("y", y)):
-        try:
-            if np.asarray(v).dtype.kind not in "iuf":
-                raise TypeError
-            v = np.array(v, dtype=np.float64, copy=True)
-        except (TypeError, ValueError):
-            raise ValueError("sample2d: %s has to be a vector of numbers" % name)
+        v = _numbers("sample2d", v, "%s has to be a vector of numbers" % name)
         if v.ndim == 0:
             v = v.reshape(1)
         if v.ndim != 1:
@@ -351,14 +353,11 @@ def fft2d(nx, ny, L=1):
     Preconditioning: the row and column sums of |K|^alpha are known in closed form, but a diagonal preconditioner of a dense
     orthogonal operator is very conservative (the sums are about 1.27 sqrt(N) at alpha = 1 where the operator's norm is 1): use
     prob.set_scaling_identity(), as the example does."""
-    for name, v, top in (("nx", nx, FFT2D_MAX_SIDE), ("ny", ny, FFT2D_MAX_SIDE), ("L", L, None)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or int(v) != v:
-            raise ValueError("fft2d: %s = %r is not an integer" % (name, v))
-        if v < 1:
-            raise ValueError("fft2d: %s = %r has to be at least 1" % (name, v))
-        if top is not None and (v > top or int(v) & (int(v) - 1)):
-            raise ValueError("fft2d: %s = %r has to be a power of two from 1 to %d" % (name, v, top))
-    nx, ny, L = int(nx), int(ny), int(L)
+    for name, v in (("nx", nx), ("ny", ny)):
+        n = _integer("fft2d", name, v)
+        if n > FFT2D_MAX_SIDE or n & (n - 1):
+            raise ValueError("fft2d: %s = %r has to be a power of two from 1 to %d" % (name, v, FFT2D_MAX_SIDE))
+    nx, ny, L = int(nx), int(ny), _integer("fft2d", "L", L)
     if 2 * L * nx * ny >= 2 ** 31:
         raise ValueError("fft2d: L = %d images of %d x %d; 2 L nx ny has to stay below 2^31" % (L, nx, ny))
     sz = [2 * L * nx * ny, 2 * L * nx * ny]
@@ -400,21 +399,11 @@ def wavelet2d(nx, ny, L=1, wavelet="haar", levels=1):
     Preconditioning: the row and column sums of |K|^alpha are computed from the filter, but a diagonal preconditioner of an orthogonal
     operator is conservative (the operator's norm is 1, the sums grow with the support of the coarse functions): use
     prob.set_scaling_identity(), as examples/wavelet_mri.py does."""
-    for name, v in (("nx", nx), ("ny", ny), ("L", L), ("levels", levels)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or int(v) != v:
-            raise ValueError("wavelet2d: %s = %r is not an integer" % (name, v))
-        if v < 1:
-            raise ValueError("wavelet2d: %s = %r has to be at least 1" % (name, v))
-    nx, ny, L, levels = int(nx), int(ny), int(L), int(levels)
+    nx, ny, L, levels = [_integer("wavelet2d", name, v) for name, v in (("nx", nx), ("ny", ny), ("L", L), ("levels", levels))]
     if isinstance(wavelet, str):
         taps = wavelet2d_taps(wavelet)
     else:
-        try:
-            if np.asarray(wavelet).dtype.kind not in "iuf":
-                raise TypeError
-            taps = np.array(wavelet, dtype=np.float64, copy=True)
-        except (TypeError, ValueError):
-            raise ValueError("wavelet2d: the wavelet has to be a name or a vector of taps")
+        taps = _numbers("wavelet2d", wavelet, "the wavelet has to be a name or a vector of taps")
         if taps.ndim != 1:
             raise ValueError("wavelet2d: the taps have to be a vector, got shape %r" % (taps.shape,))
         if taps.size < 2 or taps.size > WAVELET2D_MAX_TAPS or taps.size % 2:
@@ -454,13 +443,8 @@ def sym_gradient2d(nx, ny, L=1, w=math.sqrt(0.5)):
     differences with the boundary handling of the divergence (Bx = -Dx^T, By = -Dy^T of gradient2d's forward differences):
     exx = Bx vx, eyy = By vy, exy = w (By vx + Bx vy).  w = sqrt(1/2): the 2-norm of (exx, eyy, exy) is the Frobenius norm of the
     symmetrised Jacobian; w = 0.5: the entries of (J + J^T) / 2."""
-    for name, v in (("nx", nx), ("ny", ny), ("L", L)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or int(v) != v:
-            raise ValueError("sym_gradient2d: %s = %r is not an integer" % (name, v))
-        if v < 1:
-            raise ValueError("sym_gradient2d: %s = %r has to be at least 1" % (name, v))
-    nx, ny, L = int(nx), int(ny), int(L)
-    if isinstance(w, bool) or not isinstance(w, (int, float, np.integer, np.floating)) or not np.isfinite(w):
+    nx, ny, L = [_integer("sym_gradient2d", name, v) for name, v in (("nx", nx), ("ny", ny), ("L", L))]
+    if isinstance(w, bool) or not isinstance(w, _NUMBER) or not np.isfinite(w):
         raise ValueError("sym_gradient2d: w = %r is not a finite number" % (w,))
     w = float(w)
     if w == 0:
@@ -490,26 +474,13 @@ def tensor_gradient2d(nx, ny, L, tensor):
     values or an (ny, nx) array.  Zeros are legal (an edge that is switched off); non-finite values are refused.  With g = 1 the block is
     gradient2d bit for bit.  The device stores the k N values of the tensor and nothing per channel; the sparse matrix of the same
     operator stores 4 (k = 1, 2) or 6 (k = 3) entries with their indices per pixel and channel, once for each side."""
-    for name, v in (("nx", nx), ("ny", ny), ("L", L)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or int(v) != v:
-            raise ValueError("tensor_gradient2d: %s = %r is not an integer" % (name, v))
-        if v < 1:
-            raise ValueError("tensor_gradient2d: %s = %r has to be at least 1" % (name, v))
-    nx, ny, L = int(nx), int(ny), int(L)
+    nx, ny, L = [_integer("tensor_gradient2d", name, v) for name, v in (("nx", nx), ("ny", ny), ("L", L))]
     N = nx * ny
     if 2 * L * N > TENSOR_GRADIENT2D_MAX_SIZE:
         raise ValueError("tensor_gradient2d: 2 L nx ny = %d rows; the size has to stay within 2^53" % (2 * L * N))
 
-    def numbers(v, what):
-        try:
-            if np.asarray(v).dtype.kind not in "iuf":
-                raise TypeError
-            return np.array(v, dtype=np.float64, copy=True)
-        except (TypeError, ValueError):
-            raise ValueError("tensor_gradient2d: %s has to be an array of numbers" % what)
-
     def plane(v, what):
-        v = numbers(v, what)
+        v = _numbers("tensor_gradient2d", v, "%s has to be an array of numbers" % what)
         if v.ndim == 2 and v.shape == (ny, nx):
             v = v.reshape(-1, order="F")                   # p = y + x ny
         if v.ndim != 1 or v.size != N:
@@ -520,7 +491,7 @@ def tensor_gradient2d(nx, ny, L, tensor):
     if isinstance(tensor, (list, tuple)) and len(tensor) > 0 and not np.isscalar(tensor[0]):
         planes = [plane(v, "plane %d of the tensor" % i) for i, v in enumerate(tensor)]
     else:
-        t = numbers(tensor, "the tensor")
+        t = _numbers("tensor_gradient2d", tensor, "the tensor has to be an array of numbers")
         if t.ndim == 1:
             planes = [plane(t, "the tensor")]
         elif t.ndim == 2:

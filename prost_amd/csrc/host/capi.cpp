@@ -167,6 +167,12 @@ static std::pair<double, double> declared_size(const prost_value* d, size_t base
   if (d->cells.size() == base) return {-1.0, -1.0};
   return {GetScalarFromCell(d, base), GetScalarFromCell(d, base + 1)};
 }
+/// cell i of such data cells (declared_size has checked their count) as numbers, column-major; `message` unless it is a full matrix
+static std::vector<double> full_vector(const prost_value* d, size_t i, const char* message) {
+  const prost_value* p = d->cells[i];
+  if (!p || p->kind != PROST_VALUE_MATRIX) throw Exception(message);
+  return std::vector<double>(p->data.begin(), p->data.begin() + p->rows * p->cols);
+}
 static std::vector<const prost_value*> cell_list(const prost_value* c) {
   std::vector<const prost_value*> out;
   if (!c) throw Exception("Tried to run GetCellArray on non-existing array.");
@@ -436,88 +442,68 @@ std::map<std::string, typename Factory<T>::BlockFactory>& Factory<T>::block_reg(
         std::vector<int32_t> ptr(pm->jc.begin(), pm->jc.end()), ind(pm->ir.begin(), pm->ir.begin() + nnz);
         return BlockKronSparse<T>::CreateFromCSC(id_first != 0, row, col, diaglength, nrows, ncols, nnz, val, ptr, ind);
       };
-    // the coupling of the sublabel-accurate data term: cells { nx, ny, L, left, right }; a caller that also knows the size it means the
-    // block to have appends { nrows, ncols } and gets it checked.  Every argument check is BlockDatatermSublabel<T>::Create's.
+    // The matrix-free blocks.  A caller that also knows the size it means the block to have appends { nrows, ncols } to the data cells and
+    // gets it checked; every argument check is the block's Create's.
+    // the coupling of the sublabel-accurate data term: cells { nx, ny, L, left, right }
     reg["dataterm_sublabel"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
       const auto size = declared_size(d, 5, "BlockDatatermSublabel: the data cells are { nx, ny, L, left, right } or { nx, ny, L, left, right, nrows, ncols }.");
       return BlockDatatermSublabel<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), GetScalarFromCell(d, 3),
                                               GetScalarFromCell(d, 4), size.first, size.second);
     };
-    // 2-D convolution without a matrix: cells { nx, ny, L, kernel (ky x kx full matrix), shape }; a caller that also knows the size it means
-    // the block to have appends { nrows, ncols } and gets it checked.  Every argument check is BlockConv2D<T>::Create's.
+    // 2-D convolution: cells { nx, ny, L, kernel (ky x kx full matrix), shape }
     reg["conv2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
       const auto size = declared_size(d, 5, "BlockConv2D: the data cells are { nx, ny, L, kernel, shape } or { nx, ny, L, kernel, shape, nrows, ncols }.");
-      const prost_value* pm = d->cells[3];
-      if (!pm || pm->kind != PROST_VALUE_MATRIX) throw Exception("BlockConv2D: the window has to be a full matrix of type single or double.");
+      const std::vector<double> kernel = full_vector(d, 3, "BlockConv2D: the window has to be a full matrix of type single or double.");
       if (!d->cells[4] || d->cells[4]->kind != PROST_VALUE_STRING) throw Exception("BlockConv2D: the shape has to be a string (full, same or valid).");
-      return BlockConv2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2),
-                                    std::vector<double>(pm->data.begin(), pm->data.begin() + pm->rows * pm->cols), pm->rows, pm->cols, d->cells[4]->str,
-                                    size.first, size.second);
+      return BlockConv2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), kernel, d->cells[3]->rows, d->cells[3]->cols,
+                                    d->cells[4]->str, size.first, size.second);
     };
-    // blur and decimate without a matrix: cells { nx, ny, L, kernel (ky x kx full matrix), shape, sy, sx, py, px }; a caller that also knows
-    // the size it means the block to have appends { nrows, ncols } and gets it checked.  Every argument check is BlockConv2DStrided<T>::Create's.
+    // blur and decimate: cells { nx, ny, L, kernel (ky x kx full matrix), shape, sy, sx, py, px }
     reg["conv2d_strided"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
       const auto size = declared_size(d, 9, "BlockConv2DStrided: the data cells are { nx, ny, L, kernel, shape, sy, sx, py, px } or { nx, ny, L, kernel, shape, sy, sx, py, px, nrows, ncols }.");
-      const prost_value* pm = d->cells[3];
-      if (!pm || pm->kind != PROST_VALUE_MATRIX) throw Exception("BlockConv2DStrided: the window has to be a full matrix of type single or double.");
+      const std::vector<double> kernel = full_vector(d, 3, "BlockConv2DStrided: the window has to be a full matrix of type single or double.");
       if (!d->cells[4] || d->cells[4]->kind != PROST_VALUE_STRING) throw Exception("BlockConv2DStrided: the shape has to be a string (full, same or valid).");
-      return BlockConv2DStrided<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2),
-                                           std::vector<double>(pm->data.begin(), pm->data.begin() + pm->rows * pm->cols), pm->rows, pm->cols, d->cells[4]->str,
-                                           GetScalarFromCell(d, 5), GetScalarFromCell(d, 6), GetScalarFromCell(d, 7), GetScalarFromCell(d, 8), size.first, size.second);
+      return BlockConv2DStrided<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), kernel, d->cells[3]->rows, d->cells[3]->cols,
+                                           d->cells[4]->str, GetScalarFromCell(d, 5), GetScalarFromCell(d, 6), GetScalarFromCell(d, 7), GetScalarFromCell(d, 8), size.first,
+                                           size.second);
     };
-    // the parallel-beam projector without a matrix: cells { nx, ny, L, angles (full vector), ndet, spacing, shift }; a caller that also knows
-    // the size it means the block to have appends { nrows, ncols } and gets it checked.  Every argument check is BlockRadon2D<T>::Create's.
+    // the parallel-beam projector: cells { nx, ny, L, angles (full vector), ndet, spacing, shift }
     reg["radon2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
       const auto size = declared_size(d, 7, "BlockRadon2D: the data cells are { nx, ny, L, angles, ndet, spacing, shift } or { nx, ny, L, angles, ndet, spacing, shift, nrows, ncols }.");
-      const prost_value* pa = d->cells[3];
-      if (!pa || pa->kind != PROST_VALUE_MATRIX) throw Exception("BlockRadon2D: the angles have to be a full vector of type single or double.");
-      return BlockRadon2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2),
-                                     std::vector<double>(pa->data.begin(), pa->data.begin() + pa->rows * pa->cols), GetScalarFromCell(d, 4), GetScalarFromCell(d, 5),
-                                     GetScalarFromCell(d, 6), size.first, size.second);
+      const std::vector<double> angles = full_vector(d, 3, "BlockRadon2D: the angles have to be a full vector of type single or double.");
+      return BlockRadon2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), angles, GetScalarFromCell(d, 4),
+                                     GetScalarFromCell(d, 5), GetScalarFromCell(d, 6), size.first, size.second);
     };
-    // bilinear resampling without a matrix: cells { nx, ny, L, x, y (full vectors of the same length) }; a caller that also knows the size it
-    // means the block to have appends { nrows, ncols } and gets it checked.  Every argument check is BlockSample2D<T>::Create's.
+    // bilinear resampling: cells { nx, ny, L, x, y (full vectors of the same length) }
     reg["sample2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
       const auto size = declared_size(d, 5, "BlockSample2D: the data cells are { nx, ny, L, x, y } or { nx, ny, L, x, y, nrows, ncols }.");
-      const prost_value *px = d->cells[3], *py = d->cells[4];
-      if (!px || px->kind != PROST_VALUE_MATRIX || !py || py->kind != PROST_VALUE_MATRIX)
-        throw Exception("BlockSample2D: the positions have to be full vectors of type single or double.");
-      return BlockSample2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2),
-                                      std::vector<double>(px->data.begin(), px->data.begin() + px->rows * px->cols),
-                                      std::vector<double>(py->data.begin(), py->data.begin() + py->rows * py->cols), size.first, size.second);
+      const std::vector<double> x = full_vector(d, 3, "BlockSample2D: the positions have to be full vectors of type single or double.");
+      const std::vector<double> y = full_vector(d, 4, "BlockSample2D: the positions have to be full vectors of type single or double.");
+      return BlockSample2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), x, y, size.first, size.second);
     };
-    // the unitary 2-D Fourier transform without a matrix: cells { nx, ny, L }; a caller that also knows the size it means the block to have
-    // appends { nrows, ncols } and gets it checked.  Every argument check is BlockFFT2D<T>::Create's.
+    // the unitary 2-D Fourier transform: cells { nx, ny, L }
     reg["fft2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
       const auto size = declared_size(d, 3, "BlockFFT2D: the data cells are { nx, ny, L } or { nx, ny, L, nrows, ncols }.");
       return BlockFFT2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), size.first, size.second);
     };
-    // the orthogonal multi-level wavelet transform without a matrix: cells { nx, ny, L, taps (full vector, the low-pass filter), levels }; a
-    // caller that also knows the size it means the block to have appends { nrows, ncols } and gets it checked.  Every argument check is
-    // BlockWavelet2D<T>::Create's.
+    // the orthogonal multi-level wavelet transform: cells { nx, ny, L, taps (full vector, the low-pass filter), levels }
     reg["wavelet2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
       const auto size = declared_size(d, 5, "BlockWavelet2D: the data cells are { nx, ny, L, taps, levels } or { nx, ny, L, taps, levels, nrows, ncols }.");
-      const prost_value* pt = d->cells[3];
-      if (!pt || pt->kind != PROST_VALUE_MATRIX) throw Exception("BlockWavelet2D: the taps have to be a full vector of type single or double.");
-      return BlockWavelet2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2),
-                                       std::vector<double>(pt->data.begin(), pt->data.begin() + pt->rows * pt->cols), GetScalarFromCell(d, 4), size.first, size.second);
+      const std::vector<double> taps = full_vector(d, 3, "BlockWavelet2D: the taps have to be a full vector of type single or double.");
+      return BlockWavelet2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), taps, GetScalarFromCell(d, 4), size.first, size.second);
     };
-    // the symmetrised gradient of TGV^2 without a matrix: cells { nx, ny, L, w }; a caller that also knows the size it means the block to
-    // have appends { nrows, ncols } and gets it checked.  Every argument check is BlockSymGradient2D<T>::Create's.
+    // the symmetrised gradient of TGV^2: cells { nx, ny, L, w }
     reg["sym_gradient2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
       const auto size = declared_size(d, 4, "BlockSymGradient2D: the data cells are { nx, ny, L, w } or { nx, ny, L, w, nrows, ncols }.");
       return BlockSymGradient2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), GetScalarFromCell(d, 3), size.first,
                                            size.second);
     };
-    // K = T grad without a matrix: cells { nx, ny, L, k, tensor (full vector: k planes of nx ny values one after the other) }; a caller
-    // that also knows the size it means the block to have appends { nrows, ncols } and gets it checked.  Every argument check is
-    // BlockTensorGradient2D<T>::Create's.
+    // K = T grad: cells { nx, ny, L, k, tensor (full vector: k planes of nx ny values one after the other) }
     reg["tensor_gradient2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
       const auto size = declared_size(d, 5, "BlockTensorGradient2D: the data cells are { nx, ny, L, k, tensor } or { nx, ny, L, k, tensor, nrows, ncols }.");
-      const prost_value* pt = d->cells[4];
-      if (!pt || pt->kind != PROST_VALUE_MATRIX) throw Exception("BlockTensorGradient2D: the tensor has to be a full vector of type single or double.");
-      return BlockTensorGradient2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), GetScalarFromCell(d, 3),
-                                              std::vector<double>(pt->data.begin(), pt->data.begin() + pt->rows * pt->cols), size.first, size.second);
+      const std::vector<double> tensor = full_vector(d, 4, "BlockTensorGradient2D: the tensor has to be a full vector of type single or double.");
+      return BlockTensorGradient2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), GetScalarFromCell(d, 3), tensor, size.first,
+                                              size.second);
     };
     // the dense blocks (factory.cpp:590-601, :694-716): cell 0 is a full matrix, column-major, converted to T.  A sparse cell is refused:
     // the reference would read its value array as if it were the full matrix.

@@ -423,23 +423,122 @@ void BlockKronDense<T>::Product(T* r, const T* x, bool transpose, bool acc) {
 template class BlockKronDense<float>;
 template class BlockKronDense<double>;
 
+// ---- what the matrix-free blocks below share: refusals, argument checks, tap packing, plane sums ----
+namespace {
+const double kTwo31 = 2147483648.0;            // 2^31: planes are indexed with 32 bits
+const double kTwo53 = 9007199254740992.0;      // 2^53: counts and sizes arrive as doubles
+
+/// throws Exception("<block>: <every further argument, streamed>")
+template <class... A>
+[[noreturn]] void Refuse(const char* block, const A&... text) {
+  std::stringstream ss;
+  ss << block << ": ";
+  (ss << ... << text);
+  throw Exception(ss.str());
+}
+/// how a refusal that depends on the rounding to T ends
+template <typename T> const char* PrecisionStop() { return std::is_same<T, float>::value ? " in single precision." : "."; }
+
+typedef std::pair<const char*, double> Named;
+/// every value is an integer from 1 to `top`, else "<lead><name> = <value><tail>"
+void CheckIntegers(const char* block, std::initializer_list<Named> values, double top, const std::string& tail, const char* lead = "") {
+  for (const Named& v : values)
+    if (!(v.second >= 1) || v.second != std::floor(v.second) || v.second > top) Refuse(block, lead, v.first, " = ", v.second, tail);
+}
+void CheckBelowTwo31(const char* block, std::initializer_list<Named> values) { CheckIntegers(block, values, kTwo31 - 1, " has to be a positive integer below 2^31."); }
+/// `what`: "the window holds", "the angles hold", ..
+void CheckFinite(const char* block, const std::vector<double>& values, const char* what) {
+  for (double v : values)
+    if (!std::isfinite(v)) Refuse(block, what, " a non-finite value.");
+}
+/// a declared size (none was declared if both are negative) is rows x cols; `formula` is how the message writes that product
+void CheckDeclaredSize(const char* block, double declared_rows, double declared_cols, double rows, double cols, const char* formula, bool square = false) {
+  if (!(declared_rows >= 0 || declared_cols >= 0) || (declared_rows == rows && declared_cols == cols)) return;
+  if (square) Refuse(block, "the declared size ", declared_rows, " x ", declared_cols, " is not ", formula, " = ", rows, " square.");
+  Refuse(block, "the declared size ", declared_rows, " x ", declared_cols, " is not ", formula, " = ", rows, " x ", cols, ".");
+}
+
+// the two convolution blocks: the same window, shapes and tap records
+void CheckWindow(const char* block, const std::vector<double>& kernel, size_t ky, size_t kx) {
+  if (ky == 0 || kx == 0 || kernel.size() != ky * kx) Refuse(block, "the window is empty.");
+  if (ky > (size_t)conv2d::kMaxWindow || kx > (size_t)conv2d::kMaxWindow)
+    Refuse(block, "the window is ", ky, " x ", kx, ", windows up to ", conv2d::kMaxWindow, " x ", conv2d::kMaxWindow, " are supported.");
+  CheckFinite(block, kernel, "the window holds");
+}
+int ParseShape(const char* block, const std::string& shape) {
+  if (shape == "full") return conv2d::kFull;
+  if (shape == "same") return conv2d::kSame;
+  if (shape == "valid") return conv2d::kValid;
+  Refuse(block, "unknown shape '", shape, "' (full, same or valid).");
+}
+/// the size (my, mx) and crop offset (oy, ox) of the un-decimated convolution
+void ConvSize(const char* block, int which, double ny, double nx, size_t ky, size_t kx, long& my, long& mx, long& oy, long& ox) {
+  if (!conv2d::OutputSize(which, (long)ny, (long)nx, (long)ky, (long)kx, my, mx, oy, ox))
+    Refuse(block, "the window (", ky, " x ", kx, ") is larger than the image (", ny, " x ", nx, "): the valid part is empty.");
+}
+void CheckPlanes(const char* block, double image, double output) {
+  if (image >= kTwo31 || output >= kTwo31) Refuse(block, "a plane of ", std::max(image, output), " elements; it has to stay below 2^31.");
+}
+/// the tap records as the words that are uploaded, field by field: the padding of the fp64 record stays zero
+template <typename T>
+std::vector<int32_t> PackTaps(const std::vector<conv2d::Tap<T>>& taps) {
+  static_assert(sizeof(conv2d::Tap<T>) % sizeof(int32_t) == 0, "tap record in words");
+  const size_t words = sizeof(conv2d::Tap<T>) / sizeof(int32_t);
+  std::vector<int32_t> packed(taps.size() * words, 0);
+  for (size_t t = 0; t < taps.size(); t++) {
+    std::memcpy(&packed[t * words], &taps[t].offset, sizeof(int32_t));
+    std::memcpy(reinterpret_cast<char*>(&packed[t * words]) + offsetof(conv2d::Tap<T>, value), &taps[t].value, sizeof(T));
+  }
+  return packed;
+}
+
+/// pixel p of a column-major plane of height ny
+struct Pixel {
+  int y, x;
+  Pixel(size_t p, int ny) : y((int)(p % (size_t)ny)), x((int)(p / (size_t)ny)) {}
+};
+/// the geometry record of one direction
+template <class G> G Directed(G g, bool transpose) { g.transpose = transpose ? 1 : 0; return g; }
+/// out[c n + i] += (T)fn(i) for i < n, c < planes: one plane is computed once, on `threads` host threads, and added to every plane
+template <typename T, class F>
+void AddPlaneSums(T* out, size_t n, size_t planes, F fn, size_t threads = 1) {
+  std::vector<T> one(n);
+  const size_t parts = std::max<size_t>(std::min(n, threads), 1);
+  std::vector<std::thread> th;
+  std::exception_ptr err = nullptr;
+  std::mutex mu;
+  auto run = [&](size_t k) {
+    try { for (size_t i = n * k / parts; i < n * (k + 1) / parts; i++) one[i] = (T)fn(i); }
+    catch (...) { std::lock_guard<std::mutex> lock(mu); err = std::current_exception(); }
+  };
+  for (size_t k = 1; k < parts; k++) th.emplace_back(run, k);
+  run(0);
+  for (auto& t : th) t.join();
+  if (err) std::rethrow_exception(err);
+  for (size_t c = 0; c < planes; c++)
+    for (size_t i = 0; i < n; i++) out[c * n + i] += one[i];
+}
+/// out[c n + i] += fn(c) for i < n, c < planes: one constant per plane
+template <typename T, class F>
+void AddPlaneConstants(T* out, size_t n, size_t planes, F fn) {
+  for (size_t c = 0; c < planes; c++) {
+    const T v = fn(c);
+    for (size_t i = 0; i < n; i++) out[c * n + i] += v;
+  }
+}
+}  // namespace
+
 // ---- the coupling of the sublabel-accurate data term ----
 template <typename T>
 BlockDatatermSublabel<T>* BlockDatatermSublabel<T>::Create(size_t row, size_t col, double nx, double ny, double L, double left, double right,
                                                            double declared_rows, double declared_cols) {
-  std::stringstream ss;
-  ss << "BlockDatatermSublabel: ";
-  const double kMaxCount = 9007199254740992.0;      // 2^53: counts arrive as doubles
-  if (!(L >= 2) || L != std::floor(L) || L > kMaxCount) { ss << "L = " << L << " labels, at least 2 are needed."; throw Exception(ss.str()); }
-  if (!(nx >= 1) || !(ny >= 1) || nx != std::floor(nx) || ny != std::floor(ny) || nx * ny * (L - 1) > kMaxCount / 4) {
-    ss << "nx = " << nx << " and ny = " << ny << " have to be at least 1."; throw Exception(ss.str());
-  }
-  if (!std::isfinite(left) || !std::isfinite(right)) { ss << "the bounds left = " << left << " and right = " << right << " have to be finite."; throw Exception(ss.str()); }
-  if (!(left < right)) { ss << "left = " << left << " has to be below right = " << right << "."; throw Exception(ss.str()); }
+  const char* kName = "BlockDatatermSublabel";
+  if (!(L >= 2) || L != std::floor(L) || L > kTwo53) Refuse(kName, "L = ", L, " labels, at least 2 are needed.");
+  if (!(nx >= 1) || !(ny >= 1) || nx != std::floor(nx) || ny != std::floor(ny) || nx * ny * (L - 1) > kTwo53 / 4) Refuse(kName, "nx = ", nx, " and ny = ", ny, " have to be at least 1.");
+  if (!std::isfinite(left) || !std::isfinite(right)) Refuse(kName, "the bounds left = ", left, " and right = ", right, " have to be finite.");
+  if (!(left < right)) Refuse(kName, "left = ", left, " has to be below right = ", right, ".");
   const double size = 2 * nx * ny * (L - 1);
-  if ((declared_rows >= 0 || declared_cols >= 0) && (declared_rows != size || declared_cols != size)) {
-    ss << "the declared size " << declared_rows << " x " << declared_cols << " is not 2 nx ny (L - 1) = " << size << " square."; throw Exception(ss.str());
-  }
+  CheckDeclaredSize(kName, declared_rows, declared_cols, size, size, "2 nx ny (L - 1)", true);
   return new BlockDatatermSublabel<T>(row, col, (size_t)nx * (size_t)ny, (size_t)L, left, right);
 }
 template <typename T>
@@ -463,21 +562,11 @@ T BlockDatatermSublabel<T>::col_sum(size_t col, T alpha) const {
 }
 template <typename T>
 void BlockDatatermSublabel<T>::row_sums(T* out, T alpha) const {
-  const size_t k = L_ - 1;
-  for (size_t i = 0; i < 2 * k; i++) {
-    const T v = row_sum(i * npixels_, alpha);
-    T* o = out + i * npixels_;
-    for (size_t p = 0; p < npixels_; p++) o[p] += v;
-  }
+  AddPlaneConstants(out, npixels_, 2 * (L_ - 1), [&](size_t i) { return row_sum(i * npixels_, alpha); });
 }
 template <typename T>
 void BlockDatatermSublabel<T>::col_sums(T* out, T alpha) const {
-  const size_t k = L_ - 1;
-  for (size_t i = 0; i < 2 * k; i++) {
-    const T v = col_sum(i * npixels_, alpha);
-    T* o = out + i * npixels_;
-    for (size_t p = 0; p < npixels_; p++) o[p] += v;
-  }
+  AddPlaneConstants(out, npixels_, 2 * (L_ - 1), [&](size_t i) { return col_sum(i * npixels_, alpha); });
 }
 template <typename T>
 void BlockDatatermSublabel<T>::Product(T* r, const T* x, bool transpose, bool acc) {
@@ -492,48 +581,24 @@ template class BlockDatatermSublabel<double>;
 template <typename T>
 BlockConv2D<T>* BlockConv2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, const std::vector<double>& kernel, size_t ky, size_t kx,
                                        const std::string& shape, double declared_rows, double declared_cols) {
-  std::stringstream ss;
-  ss << "BlockConv2D: ";
-  const double kMaxPlane = 2147483648.0;      // 2^31
-  for (const auto& v : {std::make_pair("nx", nx), std::make_pair("ny", ny), std::make_pair("L", L)})
-    if (!(v.second >= 1) || v.second != std::floor(v.second) || v.second >= kMaxPlane) {
-      ss << v.first << " = " << v.second << " has to be a positive integer below 2^31."; throw Exception(ss.str());
-    }
-  if (ky == 0 || kx == 0 || kernel.size() != ky * kx) { ss << "the window is empty."; throw Exception(ss.str()); }
-  if (ky > (size_t)conv2d::kMaxWindow || kx > (size_t)conv2d::kMaxWindow) {
-    ss << "the window is " << ky << " x " << kx << ", windows up to " << conv2d::kMaxWindow << " x " << conv2d::kMaxWindow << " are supported."; throw Exception(ss.str());
-  }
-  for (double v : kernel)
-    if (!std::isfinite(v)) { ss << "the window holds a non-finite value."; throw Exception(ss.str()); }
-  int which = -1;
-  if (shape == "full") which = conv2d::kFull;
-  else if (shape == "same") which = conv2d::kSame;
-  else if (shape == "valid") which = conv2d::kValid;
-  else { ss << "unknown shape '" << shape << "' (full, same or valid)."; throw Exception(ss.str()); }
+  const char* kName = "BlockConv2D";
+  CheckBelowTwo31(kName, {{"nx", nx}, {"ny", ny}, {"L", L}});
+  CheckWindow(kName, kernel, ky, kx);
+  const int which = ParseShape(kName, shape);
   long my = 0, mx = 0, oy = 0, ox = 0;
-  if (!conv2d::OutputSize(which, (long)ny, (long)nx, (long)ky, (long)kx, my, mx, oy, ox)) {
-    ss << "the window (" << ky << " x " << kx << ") is larger than the image (" << ny << " x " << nx << "): the valid part is empty."; throw Exception(ss.str());
-  }
-  if (nx * ny >= kMaxPlane || (double)my * (double)mx >= kMaxPlane) { ss << "a plane of " << std::max(nx * ny, (double)my * (double)mx) << " elements; it has to stay below 2^31."; throw Exception(ss.str()); }
+  ConvSize(kName, which, ny, nx, ky, kx, my, mx, oy, ox);
+  CheckPlanes(kName, nx * ny, (double)my * (double)mx);
   const double rows = L * (double)my * (double)mx, cols = L * ny * nx;
-  if ((declared_rows >= 0 || declared_cols >= 0) && (declared_rows != rows || declared_cols != cols)) {
-    ss << "the declared size " << declared_rows << " x " << declared_cols << " is not L my mx x L ny nx = " << rows << " x " << cols << "."; throw Exception(ss.str());
-  }
+  CheckDeclaredSize(kName, declared_rows, declared_cols, rows, cols, "L my mx x L ny nx");
   std::unique_ptr<BlockConv2D<T>> b(new BlockConv2D<T>(row, col, (size_t)rows, (size_t)cols));
   for (int dir = 0; dir < 2; dir++) {
     b->geometry_[dir] = conv2d::MakeGeometry(which, (long)ny, (long)nx, (long)ky, (long)kx, (long)L, dir == 1);
     b->window_[dir] = conv2d::Window<T>(kernel.data(), (long)ky, (long)kx, dir == 1);
     const std::vector<conv2d::Tap<T>> taps = conv2d::CompactTaps<T>(b->window_[dir], (long)ky, (long)kx);
-    static_assert(sizeof(conv2d::Tap<T>) % sizeof(int32_t) == 0, "tap record in words");
-    b->words_[dir].assign(taps.size() * (sizeof(conv2d::Tap<T>) / sizeof(int32_t)), 0);
-    for (size_t t = 0; t < taps.size(); t++) {     // field by field: the padding of the fp64 record stays zero
-      int32_t* w = b->words_[dir].data() + t * (sizeof(conv2d::Tap<T>) / sizeof(int32_t));
-      std::memcpy(w, &taps[t].offset, sizeof(int32_t));
-      std::memcpy(reinterpret_cast<char*>(w) + offsetof(conv2d::Tap<T>, value), &taps[t].value, sizeof(T));
-    }
+    b->words_[dir] = PackTaps<T>(taps);
     b->ntaps_ = taps.size();
   }
-  if (b->ntaps_ == 0) { ss << "the window has no non-zero tap" << (std::is_same<T, float>::value ? " in single precision." : "."); throw Exception(ss.str()); }
+  if (b->ntaps_ == 0) Refuse(kName, "the window has no non-zero tap", PrecisionStop<T>());
   return b.release();
 }
 template <typename T>
@@ -543,14 +608,14 @@ void BlockConv2D<T>::Release() { for (int dir = 0; dir < 2; dir++) d_taps_[dir].
 template <typename T>
 T BlockConv2D<T>::row_sum(size_t row, T alpha) const {
   const conv2d::Geometry& g = geometry_[0];
-  const size_t p = row % ((size_t)g.dny * (size_t)g.dnx);
-  return (T)conv2d::SumAt<T>(g, window_[0], (double)alpha, (int)(p % (size_t)g.dny), (int)(p / (size_t)g.dny));
+  const Pixel at(row % ((size_t)g.dny * (size_t)g.dnx), g.dny);
+  return (T)conv2d::SumAt<T>(g, window_[0], (double)alpha, at.y, at.x);
 }
 template <typename T>
 T BlockConv2D<T>::col_sum(size_t col, T alpha) const {
   const conv2d::Geometry& g = geometry_[1];
-  const size_t p = col % ((size_t)g.dny * (size_t)g.dnx);
-  return (T)conv2d::SumAt<T>(g, window_[1], (double)alpha, (int)(p % (size_t)g.dny), (int)(p / (size_t)g.dny));
+  const Pixel at(col % ((size_t)g.dny * (size_t)g.dnx), g.dny);
+  return (T)conv2d::SumAt<T>(g, window_[1], (double)alpha, at.y, at.x);
 }
 template <typename T>
 void BlockConv2D<T>::row_sums(T* out, T alpha) const { conv2d::RowSums<T>(geometry_[0], window_[0], (double)alpha, out); }
@@ -575,61 +640,34 @@ BlockConv2DStrided<T>* BlockConv2DStrided<T>::Create(size_t row, size_t col, dou
                                                      const std::string& shape, double sy, double sx, double py, double px, double declared_rows,
                                                      double declared_cols) {
   namespace c2s = conv2d_strided;
-  std::stringstream ss;
-  ss << "BlockConv2DStrided: ";
-  const double kMaxPlane = 2147483648.0, kMaxSide = kMaxPlane - 1024 - conv2d::kMaxWindow;      // 2^31; sides leave room for a tile's halo
-  for (const auto& v : {std::make_pair("nx", nx), std::make_pair("ny", ny), std::make_pair("L", L)})
-    if (!(v.second >= 1) || v.second != std::floor(v.second) || v.second >= kMaxPlane) {
-      ss << v.first << " = " << v.second << " has to be a positive integer below 2^31."; throw Exception(ss.str());
-    }
-  if (ky == 0 || kx == 0 || kernel.size() != ky * kx) { ss << "the window is empty."; throw Exception(ss.str()); }
-  if (ky > (size_t)conv2d::kMaxWindow || kx > (size_t)conv2d::kMaxWindow) {
-    ss << "the window is " << ky << " x " << kx << ", windows up to " << conv2d::kMaxWindow << " x " << conv2d::kMaxWindow << " are supported."; throw Exception(ss.str());
-  }
-  for (double v : kernel)
-    if (!std::isfinite(v)) { ss << "the window holds a non-finite value."; throw Exception(ss.str()); }
-  int which = -1;
-  if (shape == "full") which = conv2d::kFull;
-  else if (shape == "same") which = conv2d::kSame;
-  else if (shape == "valid") which = conv2d::kValid;
-  else { ss << "unknown shape '" << shape << "' (full, same or valid)."; throw Exception(ss.str()); }
-  for (const auto& v : {std::make_pair("sy", sy), std::make_pair("sx", sx)})
-    if (!(v.second >= 1) || v.second != std::floor(v.second) || v.second > c2s::kMaxStride) {
-      ss << "the stride " << v.first << " = " << v.second << " has to be an integer from 1 to " << c2s::kMaxStride << "."; throw Exception(ss.str());
-    }
+  const char* kName = "BlockConv2DStrided";
+  const double kMaxSide = kTwo31 - 1024 - conv2d::kMaxWindow;      // sides leave room for a tile's halo
+  CheckBelowTwo31(kName, {{"nx", nx}, {"ny", ny}, {"L", L}});
+  CheckWindow(kName, kernel, ky, kx);
+  const int which = ParseShape(kName, shape);
+  CheckIntegers(kName, {{"sy", sy}, {"sx", sx}}, c2s::kMaxStride, " has to be an integer from 1 to " + std::to_string(c2s::kMaxStride) + ".", "the stride ");
   long cy = 0, cx = 0, oy = 0, ox = 0;
-  if (!conv2d::OutputSize(which, (long)ny, (long)nx, (long)ky, (long)kx, cy, cx, oy, ox)) {
-    ss << "the window (" << ky << " x " << kx << ") is larger than the image (" << ny << " x " << nx << "): the valid part is empty."; throw Exception(ss.str());
-  }
-  for (const auto& v : {std::make_pair(std::make_pair("py", py), std::min((long)sy, cy)), std::make_pair(std::make_pair("px", px), std::min((long)sx, cx))})
-    if (!(v.first.second >= 0) || v.first.second != std::floor(v.first.second) || v.first.second >= (double)v.second) {
-      ss << "the phase " << v.first.first << " = " << v.first.second << " has to be an integer from 0 to " << v.second - 1 << " (below the stride and the size of the convolution).";
-      throw Exception(ss.str());
-    }
+  ConvSize(kName, which, ny, nx, ky, kx, cy, cx, oy, ox);
+  for (const auto& v : {std::make_pair(Named("py", py), std::min((long)sy, cy)), std::make_pair(Named("px", px), std::min((long)sx, cx))})
+    if (!(v.first.second >= 0) || v.first.second != std::floor(v.first.second) || v.first.second >= (double)v.second)
+      Refuse(kName, "the phase ", v.first.first, " = ", v.first.second, " has to be an integer from 0 to ", v.second - 1, " (below the stride and the size of the convolution).");
   long my = 0, mx = 0;
   c2s::OutputSize(which, (long)ny, (long)nx, (long)ky, (long)kx, (long)sy, (long)sx, (long)py, (long)px, my, mx, oy, ox);
-  if (nx * ny >= kMaxPlane || (double)my * (double)mx >= kMaxPlane) { ss << "a plane of " << std::max(nx * ny, (double)my * (double)mx) << " elements; it has to stay below 2^31."; throw Exception(ss.str()); }
-  if (std::max(nx, ny) >= kMaxSide) { ss << "a side of " << std::max(nx, ny) << " pixels; it has to stay below 2^31 - 1055."; throw Exception(ss.str()); }
+  CheckPlanes(kName, nx * ny, (double)my * (double)mx);
+  if (std::max(nx, ny) >= kMaxSide) Refuse(kName, "a side of ", std::max(nx, ny), " pixels; it has to stay below 2^31 - 1055.");
   const double rows = L * (double)my * (double)mx, cols = L * ny * nx;
-  if ((declared_rows >= 0 || declared_cols >= 0) && (declared_rows != rows || declared_cols != cols)) {
-    ss << "the declared size " << declared_rows << " x " << declared_cols << " is not L my mx x L ny nx = " << rows << " x " << cols << "."; throw Exception(ss.str());
-  }
+  CheckDeclaredSize(kName, declared_rows, declared_cols, rows, cols, "L my mx x L ny nx");
   std::unique_ptr<BlockConv2DStrided<T>> b(new BlockConv2DStrided<T>(row, col, (size_t)rows, (size_t)cols));
   b->window_ = c2s::Window<T>(kernel.data(), (long)ky, (long)kx);
   const int tile = c2s::PickTile(sizeof(T), (int)sy, (int)sx, (int)ky, (int)kx);
-  if (tile < 0) { ss << "no tile of the table fits the window and the stride."; throw Exception(ss.str()); }
+  if (tile < 0) Refuse(kName, "no tile of the table fits the window and the stride.");
   for (int dir = 0; dir < 2; dir++) {
     b->geometry_[dir] = c2s::MakeGeometry(which, (long)ny, (long)nx, (long)ky, (long)kx, (long)sy, (long)sx, (long)py, (long)px, (long)L, dir == 1);
     const std::vector<conv2d::Tap<T>> taps = c2s::CompactTaps<T>(b->geometry_[dir], b->window_, tile);
-    b->words_[dir].assign(taps.size() * (sizeof(conv2d::Tap<T>) / sizeof(int32_t)), 0);
-    for (size_t t = 0; t < taps.size(); t++) {     // field by field: the padding of the fp64 record stays zero
-      int32_t* w = b->words_[dir].data() + t * (sizeof(conv2d::Tap<T>) / sizeof(int32_t));
-      std::memcpy(w, &taps[t].offset, sizeof(int32_t));
-      std::memcpy(reinterpret_cast<char*>(w) + offsetof(conv2d::Tap<T>, value), &taps[t].value, sizeof(T));
-    }
+    b->words_[dir] = PackTaps<T>(taps);
     b->ntaps_ = taps.size();
   }
-  if (b->ntaps_ == 0) { ss << "the window has no non-zero tap" << (std::is_same<T, float>::value ? " in single precision." : "."); throw Exception(ss.str()); }
+  if (b->ntaps_ == 0) Refuse(kName, "the window has no non-zero tap", PrecisionStop<T>());
   return b.release();
 }
 template <typename T>
@@ -639,14 +677,14 @@ void BlockConv2DStrided<T>::Release() { for (int dir = 0; dir < 2; dir++) d_taps
 template <typename T>
 T BlockConv2DStrided<T>::row_sum(size_t row, T alpha) const {
   const conv2d_strided::Geometry& g = geometry_[0];
-  const size_t p = row % ((size_t)g.my * (size_t)g.mx);
-  return (T)conv2d_strided::SumAt<T>(g, window_, (double)alpha, false, (int)(p % (size_t)g.my), (int)(p / (size_t)g.my));
+  const Pixel at(row % ((size_t)g.my * (size_t)g.mx), g.my);
+  return (T)conv2d_strided::SumAt<T>(g, window_, (double)alpha, false, at.y, at.x);
 }
 template <typename T>
 T BlockConv2DStrided<T>::col_sum(size_t col, T alpha) const {
   const conv2d_strided::Geometry& g = geometry_[0];
-  const size_t p = col % ((size_t)g.ny * (size_t)g.nx);
-  return (T)conv2d_strided::SumAt<T>(g, window_, (double)alpha, true, (int)(p % (size_t)g.ny), (int)(p / (size_t)g.ny));
+  const Pixel at(col % ((size_t)g.ny * (size_t)g.nx), g.ny);
+  return (T)conv2d_strided::SumAt<T>(g, window_, (double)alpha, true, at.y, at.x);
 }
 template <typename T>
 void BlockConv2DStrided<T>::row_sums(T* out, T alpha) const { conv2d_strided::Sums<T>(geometry_[0], window_, (double)alpha, false, out); }
@@ -670,32 +708,24 @@ template <typename T>
 BlockRadon2D<T>* BlockRadon2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, const std::vector<double>& angles, double ndet, double spacing, double shift,
                                          double declared_rows, double declared_cols) {
   namespace r2d = radon2d;
-  std::stringstream ss;
-  ss << "BlockRadon2D: ";
-  const double kMaxPlane = 2147483648.0;      // 2^31
-  for (const auto& v : {std::make_pair("nx", nx), std::make_pair("ny", ny)})
-    if (!(v.second >= 1) || v.second != std::floor(v.second) || v.second > r2d::kMaxSide) {
-      ss << v.first << " = " << v.second << " has to be an integer from 1 to " << r2d::kMaxSide << "."; throw Exception(ss.str());
-    }
-  if (!(L >= 1) || L != std::floor(L) || L >= kMaxPlane) { ss << "L = " << L << " has to be a positive integer below 2^31."; throw Exception(ss.str()); }
-  if (angles.empty()) { ss << "the angles are empty."; throw Exception(ss.str()); }
-  if (angles.size() > (size_t)r2d::kMaxAngles) { ss << angles.size() << " angles, up to " << r2d::kMaxAngles << " are supported."; throw Exception(ss.str()); }
-  for (double v : angles)
-    if (!std::isfinite(v)) { ss << "the angles hold a non-finite value."; throw Exception(ss.str()); }
-  if (!(spacing >= 0.5 && spacing <= 8)) { ss << "spacing = " << spacing << " has to be from 0.5 to 8."; throw Exception(ss.str()); }
-  if (!std::isfinite(shift)) { ss << "shift = " << shift << " has to be finite."; throw Exception(ss.str()); }
-  if (!(ndet >= 1) || ndet != std::floor(ndet) || ndet > (double)r2d::kMaxBins) { ss << "ndet = " << ndet << " has to be a positive integer below 2^31 - 1024."; throw Exception(ss.str()); }
+  const char* kName = "BlockRadon2D";
+  CheckIntegers(kName, {{"nx", nx}, {"ny", ny}}, r2d::kMaxSide, " has to be an integer from 1 to " + std::to_string(r2d::kMaxSide) + ".");
+  CheckBelowTwo31(kName, {{"L", L}});
+  if (angles.empty()) Refuse(kName, "the angles are empty.");
+  if (angles.size() > (size_t)r2d::kMaxAngles) Refuse(kName, angles.size(), " angles, up to ", r2d::kMaxAngles, " are supported.");
+  CheckFinite(kName, angles, "the angles hold");
+  if (!(spacing >= 0.5 && spacing <= 8)) Refuse(kName, "spacing = ", spacing, " has to be from 0.5 to 8.");
+  if (!std::isfinite(shift)) Refuse(kName, "shift = ", shift, " has to be finite.");
+  CheckIntegers(kName, {{"ndet", ndet}}, (double)r2d::kMaxBins, " has to be a positive integer below 2^31 - 1024.");
   const double na = (double)angles.size();
-  if (ndet * na >= kMaxPlane) { ss << "a sinogram of " << ndet * na << " elements; it has to stay below 2^31."; throw Exception(ss.str()); }
+  if (ndet * na >= kTwo31) Refuse(kName, "a sinogram of ", ndet * na, " elements; it has to stay below 2^31.");
   const double rows = L * na * ndet, cols = L * ny * nx;
-  if ((declared_rows >= 0 || declared_cols >= 0) && (declared_rows != rows || declared_cols != cols)) {
-    ss << "the declared size " << declared_rows << " x " << declared_cols << " is not L na ndet x L ny nx = " << rows << " x " << cols << "."; throw Exception(ss.str());
-  }
+  CheckDeclaredSize(kName, declared_rows, declared_cols, rows, cols, "L na ndet x L ny nx");
   std::unique_ptr<BlockRadon2D<T>> b(new BlockRadon2D<T>(row, col, (size_t)rows, (size_t)cols));
   b->geometry_ = r2d::MakeGeometry((long)ny, (long)nx, (long)L, (long)ndet, (long)angles.size(), spacing, false);
   b->table_ = r2d::MakeTable<T>((long)ny, (long)nx, (long)ndet, spacing, shift, angles);
   for (T v : b->table_)
-    if (!std::isfinite(v)) { ss << "the table of the angles is not finite" << (std::is_same<T, float>::value ? " in single precision." : "."); throw Exception(ss.str()); }
+    if (!std::isfinite(v)) Refuse(kName, "the table of the angles is not finite", PrecisionStop<T>());
   return b.release();
 }
 template <typename T>
@@ -705,56 +735,33 @@ void BlockRadon2D<T>::Release() { d_table_.clear(); }
 template <typename T>
 T BlockRadon2D<T>::row_sum(size_t row, T alpha) const {
   const radon2d::Geometry& g = geometry_;
-  const size_t p = row % ((size_t)g.ndet * (size_t)g.na);
-  return (T)radon2d::RowSum<T>(table_.data(), g, (double)alpha, (int)(p / (size_t)g.ndet), (int)(p % (size_t)g.ndet));
+  const Pixel bin(row % ((size_t)g.ndet * (size_t)g.na), g.ndet);      // bin d of angle a at d + a ndet
+  return (T)radon2d::RowSum<T>(table_.data(), g, (double)alpha, bin.x, bin.y);
 }
 template <typename T>
 T BlockRadon2D<T>::col_sum(size_t col, T alpha) const {
   const radon2d::Geometry& g = geometry_;
-  const size_t p = col % ((size_t)g.ny * (size_t)g.nx);
-  return (T)radon2d::ColSum<T>(table_.data(), g, (double)alpha, (int)(p % (size_t)g.ny), (int)(p / (size_t)g.ny));
+  const Pixel at(col % ((size_t)g.ny * (size_t)g.nx), g.ny);
+  return (T)radon2d::ColSum<T>(table_.data(), g, (double)alpha, at.y, at.x);
 }
-/// fn(i) -> the sum of element i of one plane, for i = 0 .. n - 1 on several host threads (`work` steps each); out[i + c n] += it for every plane c
-template <typename T, class F>
-static void radon2d_plane_sums(T* out, size_t n, size_t planes, size_t work, F fn) {
-  std::vector<T> one(n);
-  const size_t parts = std::min(n, ParallelChunks(n * std::max<size_t>(work, 1)));
-  std::vector<std::thread> th;
-  std::exception_ptr err = nullptr;
-  std::mutex mu;
-  auto run = [&](size_t k) {
-    try { for (size_t i = n * k / parts; i < n * (k + 1) / parts; i++) one[i] = (T)fn(i); }
-    catch (...) { std::lock_guard<std::mutex> lock(mu); err = std::current_exception(); }
-  };
-  for (size_t k = 1; k < parts; k++) th.emplace_back(run, k);
-  run(0);
-  for (auto& t : th) t.join();
-  if (err) std::rethrow_exception(err);
-  for (size_t c = 0; c < planes; c++)
-    for (size_t i = 0; i < n; i++) out[c * n + i] += one[i];
-}
+// the sums of one plane are enumerated on several host threads: a ray costs max(nx, ny) steps, a pixel na (2 m + 2)
 template <typename T>
 void BlockRadon2D<T>::row_sums(T* out, T alpha) const {
   const radon2d::Geometry& g = geometry_;
-  const T* table = table_.data();
-  radon2d_plane_sums<T>(out, (size_t)g.ndet * (size_t)g.na, (size_t)g.planes, (size_t)std::max(g.nx, g.ny), [&](size_t p) {
-    return radon2d::RowSum<T>(table, g, (double)alpha, (int)(p / (size_t)g.ndet), (int)(p % (size_t)g.ndet));
-  });
+  const size_t n = (size_t)g.ndet * (size_t)g.na;
+  AddPlaneSums(out, n, (size_t)g.planes, [&](size_t p) { return row_sum(p, alpha); }, ParallelChunks(n * (size_t)std::max(g.nx, g.ny)));
 }
 template <typename T>
 void BlockRadon2D<T>::col_sums(T* out, T alpha) const {
   const radon2d::Geometry& g = geometry_;
-  const T* table = table_.data();
-  radon2d_plane_sums<T>(out, (size_t)g.ny * (size_t)g.nx, (size_t)g.planes, (size_t)g.na * (size_t)(2 * g.m + 2), [&](size_t p) {
-    return radon2d::ColSum<T>(table, g, (double)alpha, (int)(p % (size_t)g.ny), (int)(p / (size_t)g.ny));
-  });
+  const size_t n = (size_t)g.ny * (size_t)g.nx;
+  AddPlaneSums(out, n, (size_t)g.planes, [&](size_t p) { return col_sum(p, alpha); }, ParallelChunks(n * (size_t)g.na * (size_t)(2 * g.m + 2)));
 }
 template <typename T>
 void BlockRadon2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
   if (d_table_.size() != table_.size()) throw Exception("BlockRadon2D used before Initialize().");
   static_assert(sizeof(prost_hip_radon2d_geometry) == sizeof(radon2d::Geometry), "records of prost_hip.h");
-  radon2d::Geometry g = geometry_;
-  g.transpose = transpose ? 1 : 0;
+  const radon2d::Geometry g = Directed(geometry_, transpose);
   CheckHip(Api<T>::radon2d(reinterpret_cast<const prost_hip_radon2d_geometry*>(&g), d_table_.data(), r, x, acc ? 1 : 0, CurrentStream()), "radon2d");
 }
 template class BlockRadon2D<float>;
@@ -765,24 +772,17 @@ template <typename T>
 BlockSample2D<T>* BlockSample2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, const std::vector<double>& x, const std::vector<double>& y,
                                            double declared_rows, double declared_cols) {
   namespace s2d = sample2d;
-  std::stringstream ss;
-  ss << "BlockSample2D: ";
-  const double kLimit = 2147483648.0;      // 2^31
-  for (const auto& v : {std::make_pair("nx", nx), std::make_pair("ny", ny)})
-    if (!(v.second >= 1) || v.second != std::floor(v.second) || v.second > s2d::kMaxSide) {
-      ss << v.first << " = " << v.second << " has to be an integer from 1 to " << s2d::kMaxSide << "."; throw Exception(ss.str());
-    }
-  if (!(L >= 1) || L != std::floor(L) || L >= kLimit) { ss << "L = " << L << " has to be a positive integer below 2^31."; throw Exception(ss.str()); }
-  if (x.size() != y.size()) { ss << x.size() << " x positions and " << y.size() << " y positions."; throw Exception(ss.str()); }
-  if (x.empty()) { ss << "the positions are empty."; throw Exception(ss.str()); }
+  const char* kName = "BlockSample2D";
+  CheckIntegers(kName, {{"nx", nx}, {"ny", ny}}, s2d::kMaxSide, " has to be an integer from 1 to " + std::to_string(s2d::kMaxSide) + ".");
+  CheckBelowTwo31(kName, {{"L", L}});
+  if (x.size() != y.size()) Refuse(kName, x.size(), " x positions and ", y.size(), " y positions.");
+  if (x.empty()) Refuse(kName, "the positions are empty.");
   const double m = (double)x.size();
-  if (m >= kLimit || L * m >= kLimit) { ss << "M = " << m << " samples on L = " << L << " planes; M and L M have to stay below 2^31."; throw Exception(ss.str()); }
-  for (size_t i = 0; i < x.size(); i++)
-    if (!std::isfinite(x[i]) || !std::isfinite(y[i])) { ss << "the positions hold a non-finite value."; throw Exception(ss.str()); }
+  if (m >= kTwo31 || L * m >= kTwo31) Refuse(kName, "M = ", m, " samples on L = ", L, " planes; M and L M have to stay below 2^31.");
+  CheckFinite(kName, x, "the positions hold");
+  CheckFinite(kName, y, "the positions hold");
   const double rows = L * m, cols = L * ny * nx;
-  if ((declared_rows >= 0 || declared_cols >= 0) && (declared_rows != rows || declared_cols != cols)) {
-    ss << "the declared size " << declared_rows << " x " << declared_cols << " is not L M x L ny nx = " << rows << " x " << cols << "."; throw Exception(ss.str());
-  }
+  CheckDeclaredSize(kName, declared_rows, declared_cols, rows, cols, "L M x L ny nx");
   std::unique_ptr<BlockSample2D<T>> b(new BlockSample2D<T>(row, col, (size_t)rows, (size_t)cols));
   b->geometry_ = s2d::MakeGeometry((long)ny, (long)nx, (long)x.size(), (long)L, false);
   b->pos_x_.assign(x.begin(), x.end());            // rounded once to T
@@ -801,33 +801,22 @@ T BlockSample2D<T>::row_sum(size_t row, T alpha) const {
 template <typename T>
 T BlockSample2D<T>::col_sum(size_t col, T alpha) const {
   const sample2d::Geometry& g = geometry_;
-  const size_t p = col % ((size_t)g.ny * (size_t)g.nx);
-  return (T)sample2d::ColSum<T>(pos_x_.data(), pos_y_.data(), order_.data(), cell_start_.data(), g, (double)alpha, (int)(p % (size_t)g.ny), (int)(p / (size_t)g.ny));
+  const Pixel at(col % ((size_t)g.ny * (size_t)g.nx), g.ny);
+  return (T)sample2d::ColSum<T>(pos_x_.data(), pos_y_.data(), order_.data(), cell_start_.data(), g, (double)alpha, at.y, at.x);
 }
 template <typename T>
 void BlockSample2D<T>::row_sums(T* out, T alpha) const {
-  const sample2d::Geometry& g = geometry_;
-  const size_t m = (size_t)g.m;
-  for (size_t i = 0; i < m; i++) {
-    const T s = (T)sample2d::RowSum<T>(pos_x_.data(), pos_y_.data(), g, (double)alpha, i);
-    for (size_t c = 0; c < (size_t)g.planes; c++) out[c * m + i] += s;
-  }
+  AddPlaneSums(out, (size_t)geometry_.m, (size_t)geometry_.planes, [&](size_t i) { return row_sum(i, alpha); });
 }
 template <typename T>
 void BlockSample2D<T>::col_sums(T* out, T alpha) const {
-  const sample2d::Geometry& g = geometry_;
-  const size_t n = (size_t)g.ny * (size_t)g.nx;
-  for (size_t p = 0; p < n; p++) {
-    const T s = (T)sample2d::ColSum<T>(pos_x_.data(), pos_y_.data(), order_.data(), cell_start_.data(), g, (double)alpha, (int)(p % (size_t)g.ny), (int)(p / (size_t)g.ny));
-    for (size_t c = 0; c < (size_t)g.planes; c++) out[c * n + p] += s;
-  }
+  AddPlaneSums(out, (size_t)geometry_.ny * (size_t)geometry_.nx, (size_t)geometry_.planes, [&](size_t p) { return col_sum(p, alpha); });
 }
 template <typename T>
 void BlockSample2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
   if (d_pos_x_.size() != pos_x_.size() || d_cell_start_.size() != cell_start_.size()) throw Exception("BlockSample2D used before Initialize().");
   static_assert(sizeof(prost_hip_sample2d_geometry) == sizeof(sample2d::Geometry), "records of prost_hip.h");
-  sample2d::Geometry g = geometry_;
-  g.transpose = transpose ? 1 : 0;
+  const sample2d::Geometry g = Directed(geometry_, transpose);
   CheckHip(Api<T>::sample2d(reinterpret_cast<const prost_hip_sample2d_geometry*>(&g), d_pos_x_.data(), d_pos_y_.data(), d_order_.data(), d_cell_start_.data(), r, x,
                             acc ? 1 : 0, CurrentStream()),
            "sample2d");
@@ -838,19 +827,14 @@ template class BlockSample2D<double>;
 // ---- the unitary 2-D Fourier transform, without a matrix ----
 template <typename T>
 BlockFFT2D<T>* BlockFFT2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, double declared_rows, double declared_cols) {
-  std::stringstream ss;
-  ss << "BlockFFT2D: ";
-  const double kLimit = 2147483648.0;      // 2^31
-  for (const auto& v : {std::make_pair("nx", nx), std::make_pair("ny", ny)})
-    if (!(v.second >= 1) || v.second != std::floor(v.second) || v.second > fft2d::kMaxSide || !fft2d::IsSide((long)v.second)) {
-      ss << v.first << " = " << v.second << " has to be a power of two from 1 to " << fft2d::kMaxSide << "."; throw Exception(ss.str());
-    }
-  if (!(L >= 1) || L != std::floor(L) || L >= kLimit) { ss << "L = " << L << " has to be a positive integer below 2^31."; throw Exception(ss.str()); }
+  const char* kName = "BlockFFT2D";
+  for (const Named& v : {Named("nx", nx), Named("ny", ny)})
+    if (!(v.second >= 1) || v.second != std::floor(v.second) || v.second > fft2d::kMaxSide || !fft2d::IsSide((long)v.second))
+      Refuse(kName, v.first, " = ", v.second, " has to be a power of two from 1 to ", fft2d::kMaxSide, ".");
+  CheckBelowTwo31(kName, {{"L", L}});
   const double size = 2 * L * ny * nx;
-  if (size >= kLimit) { ss << "L = " << L << " images of " << nx << " x " << ny << "; 2 L nx ny has to stay below 2^31."; throw Exception(ss.str()); }
-  if ((declared_rows >= 0 || declared_cols >= 0) && (declared_rows != size || declared_cols != size)) {
-    ss << "the declared size " << declared_rows << " x " << declared_cols << " is not 2 L ny nx x 2 L ny nx = " << size << " x " << size << "."; throw Exception(ss.str());
-  }
+  if (size >= kTwo31) Refuse(kName, "L = ", L, " images of ", nx, " x ", ny, "; 2 L nx ny has to stay below 2^31.");
+  CheckDeclaredSize(kName, declared_rows, declared_cols, size, size, "2 L ny nx x 2 L ny nx");
   std::unique_ptr<BlockFFT2D<T>> b(new BlockFFT2D<T>(row, col, (size_t)size, (size_t)size));
   b->geometry_ = fft2d::MakeGeometry((long)ny, (long)nx, (long)L, false);
   b->table_ = fft2d::MakeTable<T>(fft2d::TableSize((int)ny, (int)nx));
@@ -864,8 +848,8 @@ void BlockFFT2D<T>::Release() { d_table_.clear(); d_work_.clear(); }
 template <typename T>
 T BlockFFT2D<T>::row_sum(size_t row, T alpha) const {
   const fft2d::Geometry& g = geometry_;
-  const size_t q = row % ((size_t)g.ny * (size_t)g.nx);
-  const int l = fft2d::PeriodLog2((int)(q % (size_t)g.ny), (int)(q / (size_t)g.ny), g.ny, g.nx);
+  const Pixel at(row % ((size_t)g.ny * (size_t)g.nx), g.ny);
+  const int l = fft2d::PeriodLog2(at.y, at.x, g.ny, g.nx);
   return (T)(alpha == (T)1 ? sums1_[l] : fft2d::ClassSum(g.ny, g.nx, (double)alpha, l));      // any other alpha: that one class, g terms
 }
 template <typename T>
@@ -873,18 +857,16 @@ void BlockFFT2D<T>::row_sums(T* out, T alpha) const {
   const fft2d::Geometry& g = geometry_;
   double sums[fft2d::kMaxLog2 + 1];
   fft2d::SumTable(g.ny, g.nx, (double)alpha, sums);
-  const size_t n = (size_t)g.ny * (size_t)g.nx;
-  for (size_t q = 0; q < n; q++) {
-    const T s = (T)sums[fft2d::PeriodLog2((int)(q % (size_t)g.ny), (int)(q / (size_t)g.ny), g.ny, g.nx)];
-    for (size_t c = 0; c < 2 * (size_t)g.planes; c++) out[c * n + q] += s;
-  }
+  AddPlaneSums(out, (size_t)g.ny * (size_t)g.nx, 2 * (size_t)g.planes, [&](size_t q) {
+    const Pixel at(q, g.ny);
+    return sums[fft2d::PeriodLog2(at.y, at.x, g.ny, g.nx)];
+  });
 }
 template <typename T>
 void BlockFFT2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
   if (d_table_.size() != table_.size() || d_work_.size() != this->nrows()) throw Exception("BlockFFT2D used before Initialize().");
   static_assert(sizeof(prost_hip_fft2d_geometry) == sizeof(fft2d::Geometry), "records of prost_hip.h");
-  fft2d::Geometry g = geometry_;
-  g.transpose = transpose ? 1 : 0;
+  const fft2d::Geometry g = Directed(geometry_, transpose);
   CheckHip(Api<T>::fft2d(reinterpret_cast<const prost_hip_fft2d_geometry*>(&g), d_table_.data(), d_work_.data(), r, x, acc ? 1 : 0, CurrentStream()), "fft2d");
 }
 template class BlockFFT2D<float>;
@@ -895,22 +877,16 @@ template <typename T>
 BlockWavelet2D<T>* BlockWavelet2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, const std::vector<double>& taps, double levels,
                                              double declared_rows, double declared_cols) {
   namespace w2d = wavelet2d;
-  std::stringstream ss;
-  ss << "BlockWavelet2D: ";
-  for (double v : taps)
-    if (!std::isfinite(v)) { ss << "the taps hold a non-finite value."; throw Exception(ss.str()); }
-  if (const char* why = w2d::CheckShape(ny, nx, L, levels, (double)taps.size())) {
-    ss << why << " (nx = " << nx << ", ny = " << ny << ", L = " << L << ", levels = " << levels << ", " << taps.size() << " taps)."; throw Exception(ss.str());
-  }
+  const char* kName = "BlockWavelet2D";
+  CheckFinite(kName, taps, "the taps hold");
+  if (const char* why = w2d::CheckShape(ny, nx, L, levels, (double)taps.size()))
+    Refuse(kName, why, " (nx = ", nx, ", ny = ", ny, ", L = ", L, ", levels = ", levels, ", ", taps.size(), " taps).");
   const double defect = w2d::OrthoDefect(taps.data(), (int)taps.size());
-  if (!(defect <= w2d::kOrthoTolerance)) {
-    ss << "the taps are not orthonormal: |sum_k h[k] h[k+2l] - delta_l| = " << defect << " for some l, above " << w2d::kOrthoTolerance
-       << " (taps rounded from exact values miss by about 1e-15; a table truncated to fewer digits is refused)."; throw Exception(ss.str());
-  }
+  if (!(defect <= w2d::kOrthoTolerance))
+    Refuse(kName, "the taps are not orthonormal: |sum_k h[k] h[k+2l] - delta_l| = ", defect, " for some l, above ", w2d::kOrthoTolerance,
+           " (taps rounded from exact values miss by about 1e-15; a table truncated to fewer digits is refused).");
   const double size = L * ny * nx;
-  if ((declared_rows >= 0 || declared_cols >= 0) && (declared_rows != size || declared_cols != size)) {
-    ss << "the declared size " << declared_rows << " x " << declared_cols << " is not L ny nx x L ny nx = " << size << " x " << size << "."; throw Exception(ss.str());
-  }
+  CheckDeclaredSize(kName, declared_rows, declared_cols, size, size, "L ny nx x L ny nx");
   std::unique_ptr<BlockWavelet2D<T>> b(new BlockWavelet2D<T>(row, col, (size_t)size, (size_t)size));
   b->geometry_ = w2d::MakeGeometry((long)ny, (long)nx, (long)L, (long)levels, (long)taps.size(), false);
   b->taps64_ = taps;
@@ -933,42 +909,29 @@ template <typename T>
 T BlockWavelet2D<T>::row_sum(size_t row, T alpha) const {
   const wavelet2d::Geometry& g = geometry_;
   Tables((double)alpha);
-  const size_t q = row % ((size_t)g.ny * (size_t)g.nx);
-  return (T)wavelet2d::RowSum(g, tables_y_, tables_x_, (int)(q % (size_t)g.ny), (int)(q / (size_t)g.ny));
+  const Pixel at(row % ((size_t)g.ny * (size_t)g.nx), g.ny);
+  return (T)wavelet2d::RowSum(g, tables_y_, tables_x_, at.y, at.x);
 }
 template <typename T>
 T BlockWavelet2D<T>::col_sum(size_t col, T alpha) const {
   const wavelet2d::Geometry& g = geometry_;
   Tables((double)alpha);
-  const size_t p = col % ((size_t)g.ny * (size_t)g.nx);
-  return (T)wavelet2d::ColSum(g, tables_y_, tables_x_, (int)(p % (size_t)g.ny), (int)(p / (size_t)g.ny));
+  const Pixel at(col % ((size_t)g.ny * (size_t)g.nx), g.ny);
+  return (T)wavelet2d::ColSum(g, tables_y_, tables_x_, at.y, at.x);
 }
 template <typename T>
 void BlockWavelet2D<T>::row_sums(T* out, T alpha) const {
-  const wavelet2d::Geometry& g = geometry_;
-  Tables((double)alpha);
-  const size_t n = (size_t)g.ny * (size_t)g.nx;
-  for (size_t q = 0; q < n; q++) {
-    const T s = (T)wavelet2d::RowSum(g, tables_y_, tables_x_, (int)(q % (size_t)g.ny), (int)(q / (size_t)g.ny));
-    for (size_t c = 0; c < (size_t)g.planes; c++) out[c * n + q] += s;
-  }
+  AddPlaneSums(out, (size_t)geometry_.ny * (size_t)geometry_.nx, (size_t)geometry_.planes, [&](size_t q) { return row_sum(q, alpha); });
 }
 template <typename T>
 void BlockWavelet2D<T>::col_sums(T* out, T alpha) const {
-  const wavelet2d::Geometry& g = geometry_;
-  Tables((double)alpha);
-  const size_t n = (size_t)g.ny * (size_t)g.nx;
-  for (size_t p = 0; p < n; p++) {
-    const T s = (T)wavelet2d::ColSum(g, tables_y_, tables_x_, (int)(p % (size_t)g.ny), (int)(p / (size_t)g.ny));
-    for (size_t c = 0; c < (size_t)g.planes; c++) out[c * n + p] += s;
-  }
+  AddPlaneSums(out, (size_t)geometry_.ny * (size_t)geometry_.nx, (size_t)geometry_.planes, [&](size_t p) { return col_sum(p, alpha); });
 }
 template <typename T>
 void BlockWavelet2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
   if (d_work_.size() != wavelet2d::WorkSize(geometry_)) throw Exception("BlockWavelet2D used before Initialize().");
   static_assert(sizeof(prost_hip_wavelet2d_geometry) == sizeof(wavelet2d::Geometry), "records of prost_hip.h");
-  wavelet2d::Geometry g = geometry_;
-  g.transpose = transpose ? 1 : 0;
+  const wavelet2d::Geometry g = Directed(geometry_, transpose);
   CheckHip(Api<T>::wavelet2d(reinterpret_cast<const prost_hip_wavelet2d_geometry*>(&g), taps_.data(), d_work_.data(), r, x, acc ? 1 : 0, CurrentStream()), "wavelet2d");
 }
 template class BlockWavelet2D<float>;
@@ -977,24 +940,15 @@ template class BlockWavelet2D<double>;
 // ---- the symmetrised gradient of TGV^2, without a matrix ----
 template <typename T>
 BlockSymGradient2D<T>* BlockSymGradient2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, double w, double declared_rows, double declared_cols) {
-  std::stringstream ss;
-  ss << "BlockSymGradient2D: ";
-  const double kMaxSize = 9007199254740992.0;      // 2^53: sizes travel as doubles
-  for (const auto& v : {std::make_pair("nx", nx), std::make_pair("ny", ny), std::make_pair("L", L)})
-    if (!(v.second >= 1) || v.second != std::floor(v.second) || v.second > kMaxSize) {
-      ss << v.first << " = " << v.second << " has to be a positive integer."; throw Exception(ss.str());
-    }
-  if (!std::isfinite(w)) { ss << "w = " << w << " has to be finite."; throw Exception(ss.str()); }
-  if (w == 0) { ss << "w has to be non-zero."; throw Exception(ss.str()); }
+  const char* kName = "BlockSymGradient2D";
+  CheckIntegers(kName, {{"nx", nx}, {"ny", ny}, {"L", L}}, kTwo53, " has to be a positive integer.");
+  if (!std::isfinite(w)) Refuse(kName, "w = ", w, " has to be finite.");
+  if (w == 0) Refuse(kName, "w has to be non-zero.");
   const T wt = sym_gradient2d::RoundWeight<T>(w);
-  if (wt == (T)0 || !std::isfinite((double)wt)) {
-    ss << "w = " << w << " is zero or not finite" << (std::is_same<T, float>::value ? " in single precision." : "."); throw Exception(ss.str());
-  }
+  if (wt == (T)0 || !std::isfinite((double)wt)) Refuse(kName, "w = ", w, " is zero or not finite", PrecisionStop<T>());
   const double rows = 3 * L * nx * ny, cols = 2 * L * nx * ny;
-  if (!(3 * L * (nx * ny) <= kMaxSize) || !(nx * ny <= kMaxSize)) { ss << "3 L nx ny = " << rows << " rows; the size has to stay within 2^53."; throw Exception(ss.str()); }
-  if ((declared_rows >= 0 || declared_cols >= 0) && (declared_rows != rows || declared_cols != cols)) {
-    ss << "the declared size " << declared_rows << " x " << declared_cols << " is not 3 L nx ny x 2 L nx ny = " << rows << " x " << cols << "."; throw Exception(ss.str());
-  }
+  if (!(3 * L * (nx * ny) <= kTwo53) || !(nx * ny <= kTwo53)) Refuse(kName, "3 L nx ny = ", rows, " rows; the size has to stay within 2^53.");
+  CheckDeclaredSize(kName, declared_rows, declared_cols, rows, cols, "3 L nx ny x 2 L nx ny");
   return new BlockSymGradient2D<T>(row, col, (size_t)nx, (size_t)ny, (size_t)L, w);
 }
 template <typename T>
@@ -1020,30 +974,19 @@ template class BlockSymGradient2D<double>;
 template <typename T>
 BlockTensorGradient2D<T>* BlockTensorGradient2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, double mode, const std::vector<double>& tensor,
                                                            double declared_rows, double declared_cols) {
-  std::stringstream ss;
-  ss << "BlockTensorGradient2D: ";
-  const double kMaxSize = 9007199254740992.0;      // 2^53: sizes travel as doubles
-  for (const auto& v : {std::make_pair("nx", nx), std::make_pair("ny", ny), std::make_pair("L", L)})
-    if (!(v.second >= 1) || v.second != std::floor(v.second) || v.second > kMaxSize) {
-      ss << v.first << " = " << v.second << " has to be a positive integer."; throw Exception(ss.str());
-    }
-  if (!(mode == 1 || mode == 2 || mode == 3)) { ss << "the tensor has k = " << mode << " planes; k has to be 1 (scalar), 2 (per axis) or 3 (symmetric tensor)."; throw Exception(ss.str()); }
+  const char* kName = "BlockTensorGradient2D";
+  CheckIntegers(kName, {{"nx", nx}, {"ny", ny}, {"L", L}}, kTwo53, " has to be a positive integer.");
+  if (!(mode == 1 || mode == 2 || mode == 3)) Refuse(kName, "the tensor has k = ", mode, " planes; k has to be 1 (scalar), 2 (per axis) or 3 (symmetric tensor).");
   const double rows = 2 * L * nx * ny, cols = L * nx * ny;
-  if (!(2 * L * (nx * ny) <= kMaxSize) || !(nx * ny <= kMaxSize)) { ss << "2 L nx ny = " << rows << " rows; the size has to stay within 2^53."; throw Exception(ss.str()); }
-  if ((double)tensor.size() != mode * nx * ny) {
-    ss << "the tensor holds " << tensor.size() << " values, not k = " << mode << " planes of nx ny = " << nx * ny << "."; throw Exception(ss.str());
-  }
-  if ((declared_rows >= 0 || declared_cols >= 0) && (declared_rows != rows || declared_cols != cols)) {
-    ss << "the declared size " << declared_rows << " x " << declared_cols << " is not 2 L nx ny x L nx ny = " << rows << " x " << cols << "."; throw Exception(ss.str());
-  }
+  if (!(2 * L * (nx * ny) <= kTwo53) || !(nx * ny <= kTwo53)) Refuse(kName, "2 L nx ny = ", rows, " rows; the size has to stay within 2^53.");
+  if ((double)tensor.size() != mode * nx * ny) Refuse(kName, "the tensor holds ", tensor.size(), " values, not k = ", mode, " planes of nx ny = ", nx * ny, ".");
+  CheckDeclaredSize(kName, declared_rows, declared_cols, rows, cols, "2 L nx ny x L nx ny");
   std::unique_ptr<BlockTensorGradient2D<T>> b(new BlockTensorGradient2D<T>(row, col, (size_t)nx, (size_t)ny, (size_t)L, (int)mode));
   b->tensor_.resize(tensor.size());
   for (size_t i = 0; i < tensor.size(); i++) {
     const T t = (T)tensor[i];                       // rounded once
-    if (!std::isfinite((double)t)) {
-      ss << "value " << i % (size_t)(nx * ny) << " of plane " << i / (size_t)(nx * ny) << " of the tensor, " << tensor[i] << ", is not finite"
-         << (std::is_same<T, float>::value ? " in single precision." : "."); throw Exception(ss.str());
-    }
+    if (!std::isfinite((double)t))
+      Refuse(kName, "value ", i % (size_t)(nx * ny), " of plane ", i / (size_t)(nx * ny), " of the tensor, ", tensor[i], ", is not finite", PrecisionStop<T>());
     b->tensor_[i] = t;
   }
   return b.release();

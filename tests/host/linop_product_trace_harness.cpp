@@ -4,7 +4,8 @@
 // a memcpy, and every mocked call appends one line to a trace -- the entry point, every pointer as the ORDINAL of the allocation it
 // points into (prost_hip_malloc numbers them in the order they are made) plus its byte offset ("-" is null), every size and int
 // argument, every double in %a, and for every device array the call is given (CSR arrays, pattern tables, anchors, gamma, tap tables,
-// the conv2d geometry record, ...) its length and a 64-bit FNV-1a digest of its bytes.  Per placement the host-only answers follow:
+// per-angle tables, positions and buckets, twiddle tables, tensor planes, ...) and every host record (the geometry records, the wavelet
+// taps) its length and a 64-bit FNV-1a digest of its bytes.  Per placement the host-only answers follow:
 // sizes, gpu_mem_amount, describe / stencil_shape / uniform_sums, and every row and column sum at alpha 1 and 2 (runs of equal values
 // as COUNTxVALUE) with whether the bulk forms add exactly those.
 //
@@ -100,6 +101,43 @@ static int sublabel(const char* name, size_t e, const void* r, const void* x, si
 static int conv(const char* name, size_t tap_bytes, const prost_hip_conv2d_geometry* g, const void* taps, size_t ntaps, const void* r, const void* x, int acc) {
   logf("%s geometry=host[%zu fnv=%016llx] taps=%s ntaps=%zu res=%s rhs=%s acc=%d", name, sizeof(*g), Fnv(g, sizeof(*g)), AA(taps, ntaps, tap_bytes), ntaps, PP(r), PP(x), acc); return 0;
 }
+// a record or array the ABI reads on the host before the call returns
+static std::string H(const void* p, size_t bytes) {
+  char buf[64];
+  snprintf(buf, sizeof(buf), "host[%zu fnv=%016llx]", bytes, Fnv(p, bytes));
+  return buf;
+}
+#define HH(p, n) R(H(p, n))
+static int conv_strided(const char* name, size_t tap_bytes, const prost_hip_conv2d_strided_geometry* g, const void* taps, size_t ntaps, const void* r, const void* x, int acc) {
+  logf("%s geometry=%s transpose=%d taps=%s ntaps=%zu res=%s rhs=%s acc=%d", name, HH(g, sizeof(*g)), (int)g->transpose, AA(taps, ntaps, tap_bytes), ntaps, PP(r), PP(x), acc); return 0;
+}
+static int radon(const char* name, size_t e, const prost_hip_radon2d_geometry* g, const void* table, const void* r, const void* x, int acc) {
+  logf("%s geometry=%s transpose=%d table=%s res=%s rhs=%s acc=%d", name, HH(g, sizeof(*g)), (int)g->transpose, AA(table, (size_t)g->na * PROST_HIP_RADON2D_TABLE_WIDTH, e), PP(r), PP(x),
+       acc); return 0;
+}
+static int sample(const char* name, size_t e, const prost_hip_sample2d_geometry* g, const void* px, const void* py, const int32_t* order, const int32_t* cell_start, const void* r,
+                  const void* x, int acc) {
+  const size_t m = (size_t)g->m, cells = ((size_t)g->ny + 1) * ((size_t)g->nx + 1);
+  logf("%s geometry=%s transpose=%d pos_x=%s pos_y=%s order=%s cell_start=%s res=%s rhs=%s acc=%d", name, HH(g, sizeof(*g)), (int)g->transpose, AA(px, m, e), AA(py, m, e),
+       AA(order, m, 4), AA(cell_start, cells + 1, 4), PP(r), PP(x), acc); return 0;
+}
+static int fft(const char* name, size_t e, const prost_hip_fft2d_geometry* g, const void* table, const void* work, const void* r, const void* x, int acc) {
+  const size_t n = (size_t)(g->ny > g->nx ? g->ny : g->nx), values = 2 * (size_t)g->planes * (size_t)g->ny * (size_t)g->nx;
+  logf("%s geometry=%s transpose=%d table=%s work=%s res=%s rhs=%s acc=%d", name, HH(g, sizeof(*g)), (int)g->transpose, AA(table, 2 * n, e), AA(work, values, e), PP(r), PP(x), acc);
+  return 0;
+}
+// planes (C(1) + C(2)) values, C(j) the corner of a plane after j levels (a side of 1 stays 1)
+static size_t WaveletWorkValues(const prost_hip_wavelet2d_geometry* g) {
+  auto side = [](int n, int j) { return (size_t)(n > 1 ? n >> j : 1); };
+  return (size_t)g->planes * (side(g->ny, 1) * side(g->nx, 1) + side(g->ny, 2) * side(g->nx, 2));
+}
+static int wavelet(const char* name, size_t e, const prost_hip_wavelet2d_geometry* g, const void* taps, const void* work, size_t work_values, const void* r, const void* x, int acc) {
+  logf("%s geometry=%s transpose=%d taps=%s work=%s res=%s rhs=%s acc=%d", name, HH(g, sizeof(*g)), (int)g->transpose, HH(taps, (size_t)g->ntaps * e), AA(work, work_values, e), PP(r),
+       PP(x), acc); return 0;
+}
+static int tensorgrad(const char* name, size_t e, const void* r, const void* x, const void* tensor, size_t nx, size_t ny, size_t L, int mode, int transpose, int acc) {
+  logf("%s res=%s rhs=%s tensor=%s nx=%zu ny=%zu L=%zu mode=%d transpose=%d acc=%d", name, PP(r), PP(x), AA(tensor, (size_t)mode * nx * ny, e), nx, ny, L, mode, transpose, acc); return 0;
+}
 static int symgrad(const char* name, const void* r, const void* x, size_t nx, size_t ny, size_t L, double w, int transpose, int acc) {
   logf("%s res=%s rhs=%s nx=%zu ny=%zu L=%zu w=%a transpose=%d acc=%d", name, PP(r), PP(x), nx, ny, L, w, transpose, acc); return 0;
 }
@@ -154,7 +192,21 @@ size_t prost_hip_dense_gemv_workspace_bytes(size_t nrows, size_t ncols) { return
   int prost_hip_conv2d_##S(const prost_hip_conv2d_geometry* g, const prost_hip_conv2d_tap_##S* taps, size_t nt, T* r, const T* x, int acc, void*) {                         \
     return conv("conv2d_" #S, sizeof(prost_hip_conv2d_tap_##S), g, taps, nt, r, x, acc);                                                                                    \
   }                                                                                                                                                                         \
-  int prost_hip_linop_sym_gradient2d_##S(T* r, const T* x, size_t nx, size_t ny, size_t L, double w, int t, int acc, void*) { return symgrad("linop_sym_gradient2d_" #S, r, x, nx, ny, L, w, t, acc); }
+  int prost_hip_linop_sym_gradient2d_##S(T* r, const T* x, size_t nx, size_t ny, size_t L, double w, int t, int acc, void*) { return symgrad("linop_sym_gradient2d_" #S, r, x, nx, ny, L, w, t, acc); } \
+  int prost_hip_conv2d_strided_##S(const prost_hip_conv2d_strided_geometry* g, const prost_hip_conv2d_tap_##S* taps, size_t nt, T* r, const T* x, int acc, void*) {         \
+    return conv_strided("conv2d_strided_" #S, sizeof(prost_hip_conv2d_tap_##S), g, taps, nt, r, x, acc);                                                                    \
+  }                                                                                                                                                                         \
+  int prost_hip_radon2d_##S(const prost_hip_radon2d_geometry* g, const T* table, T* r, const T* x, int acc, void*) { return radon("radon2d_" #S, sizeof(T), g, table, r, x, acc); } \
+  int prost_hip_sample2d_##S(const prost_hip_sample2d_geometry* g, const T* px, const T* py, const int32_t* o, const int32_t* cs, T* r, const T* x, int acc, void*) {        \
+    return sample("sample2d_" #S, sizeof(T), g, px, py, o, cs, r, x, acc);                                                                                                  \
+  }                                                                                                                                                                         \
+  int prost_hip_fft2d_##S(const prost_hip_fft2d_geometry* g, const T* table, T* work, T* r, const T* x, int acc, void*) { return fft("fft2d_" #S, sizeof(T), g, table, work, r, x, acc); } \
+  int prost_hip_wavelet2d_##S(const prost_hip_wavelet2d_geometry* g, const T* taps, T* work, T* r, const T* x, int acc, void*) {                                           \
+    return wavelet("wavelet2d_" #S, sizeof(T), g, taps, work, WaveletWorkValues(g), r, x, acc);                                                                            \
+  }                                                                                                                                                                         \
+  int prost_hip_linop_tensor_gradient2d_##S(T* r, const T* x, const T* tensor, size_t nx, size_t ny, size_t L, int mode, int t, int acc, void*) {                           \
+    return tensorgrad("linop_tensor_gradient2d_" #S, sizeof(T), r, x, tensor, nx, ny, L, mode, t, acc);                                                                     \
+  }
 LINOP_MOCKS(float, f32)
 LINOP_MOCKS(double, f64)
 #undef LINOP_MOCKS
@@ -337,6 +389,22 @@ static std::vector<Scenario> AllScenarios() {
   BLOCK("dataterm_sublabel", BlockDatatermSublabel<T>::Create(row, col, 2, 3, 4, 0.0, 1.0))
   BLOCK("conv2d", BlockConv2D<T>::Create(row, col, 4, 5, 2, DenseData(3, 2), 3, 2, "same"))
   BLOCK("sym_gradient2d", BlockSymGradient2D<T>::Create(row, col, 3, 4, 2, 0.5))
+  // the blocks added after sym_gradient2d: the smallest shapes that reach every branch of their host code
+  std::vector<double> window = DenseData(3, 3);
+  window[4] = 0;                                         // one zero tap
+  BLOCK("conv2d_strided", BlockConv2DStrided<T>::Create(row, col, 7, 5, 2, window, 3, 3, "same", 2, 2, 1, 0))
+  // a row-marched, a column-marched and an obtuse angle; the default detector length 2 ceil(hypot(6, 5) / 2) + 1
+  BLOCK("radon2d", BlockRadon2D<T>::Create(row, col, 6, 5, 2, std::vector<double>{0, 0.7, 2.2}, 9, 1, 0.25))
+  // a pixel centre, two positions in one cell, one in the border strip [-1, 0), one outside (a zero row), two more
+  const std::vector<double> sx = {2, 1.25, 1.75, -0.5, 7, 3.5, 0.25}, sy = {1, 0.5, 0.25, 1.5, 2, 2.5, 2.875};
+  BLOCK("sample2d", BlockSample2D<T>::Create(row, col, 5, 4, 2, sx, sy))
+  BLOCK("fft2d", BlockFFT2D<T>::Create(row, col, 4, 8, 2))
+  const std::vector<double> db2 = {0.48296291314453416, 0.83651630373780790, 0.22414386804201339, -0.12940952255126037};
+  BLOCK("wavelet2d", BlockWavelet2D<T>::Create(row, col, 8, 4, 2, db2, 1))
+  std::vector<double> tensor3 = DenseData(12, 3), tensor1 = DenseData(12, 1);
+  tensor3[17] = 0;                                       // an edge that is switched off
+  BLOCK("tensor_gradient2d.k3", BlockTensorGradient2D<T>::Create(row, col, 4, 3, 2, 3, tensor3))
+  BLOCK("tensor_gradient2d.k1", BlockTensorGradient2D<T>::Create(row, col, 4, 3, 2, 1, tensor1))
   BLOCK("diags", new BlockDiags<T>(row, col, 4, 5, 3, std::vector<int64_t>{1, -1, 0}, As<T>(std::vector<double>{0.5, -2, 1.25})))
   BLOCK("zero", new BlockZero<T>(row, col, 3, 4))
   return all;

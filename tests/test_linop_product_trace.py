@@ -3,20 +3,24 @@
 tests/host/linop_product_trace_harness.cpp compiles prost_amd/csrc/host/{common,linop}.cpp against a recording mock of
 include/prost_hip.h (device memory is host memory, an upload is a memcpy) and prints, per block and placement, one line per ABI call:
 the entry point, every pointer as allocation ordinal + byte offset, every size and flag, every double in hex, and length + FNV digest
-of every device array passed (CSR arrays, pattern tables, anchors, gamma, tap tables, the conv2d geometry record).  Host-only answers
+of every device array passed (CSR arrays, pattern tables, anchors, gamma, tap tables, per-angle tables, positions and bucket tables,
+twiddle tables, tensor planes) and of every host record (the geometry records, the wavelet taps).  Host-only answers
 follow: sizes, gpu_mem_amount, describe / stencil_shape / uniform_sums, every row and column sum at alpha 1 and 2 and whether
 row_sums / col_sums add exactly those, and the exception text of a product before Initialize().
 
 Blocks: gradient2d / gradient3d (label_first 0 and 1), sparse (a 5 x 7 matrix that stays CSR, the 300 x 300 forward difference that runs
 from row patterns, a 300 x 600 matrix that runs from anchored patterns, a matrix without entries), both sparse and both dense Kronecker
-blocks, dense, dataterm_sublabel, conv2d, sym_gradient2d, diags and zero, in float and double; each alone at (0, 0), as the second of
+blocks, dense, dataterm_sublabel, conv2d, sym_gradient2d, conv2d_strided, radon2d, sample2d, fft2d, wavelet2d, tensor_gradient2d (k = 3
+and k = 1), diags and zero, in float and double; each alone at (0, 0), as the second of
 two copies stacked below the first and as the second of two side by side, through LinearOperator::Eval / EvalAdjoint and
 DualLinearOperator at beta 0 and 1 -- so the exclusive, first-writer and accumulate paths reach all four evaluation virtuals.
 
 tests/golden/linop_product_traces.txt holds what the harness printed at commit c7472ab ("sym_gradient2d: matrix-free symmetrised
 gradient block for TGV"), where every block still wrote out its four evaluation virtuals and BlockSparse kept K and K^T as parallel
-member lists: the text of a few placements, and for every placement of every scenario its number of lines and a SHA-256 (the whole
-output is 8 366 lines, as in pdhg_launch_traces.txt).  A host-side change that is meant to leave every ABI call as it is must leave this
+member lists: the text of a few placements, and for every placement of every scenario its number of lines and a SHA-256 (as in
+pdhg_launch_traces.txt).  The lines of the six blocks from conv2d_strided to tensor_gradient2d were added at commit a60a5bd
+("tensor_gradient2d: matrix-free weighted / anisotropic gradient block") with the library sources of that commit; the lines from before
+did not change, and the whole output is 11 332 lines.  A host-side change that is meant to leave every ABI call as it is must leave this
 file as it is.  After a change that is MEANT to alter a call: python tests/test_linop_product_trace.py --regenerate, and review the diff.
 
 The harness is a stand-alone program and runs under AddressSanitizer and UndefinedBehaviorSanitizer: the mock reads every array at the
@@ -36,13 +40,14 @@ GOLDEN = os.path.join(host_harness.ROOT, "tests", "golden", "linop_product_trace
 HARNESS = "linop_product_trace_harness"
 EXTRA_FLAGS = ["-pthread", "-I" + os.path.join(host_harness.ROOT, "prost_amd", "csrc", "host"), "-Wl,--unresolved-symbols=ignore-all"]
 BLOCKS = ["gradient2d", "gradient3d", "sparse", "sparse_kron_id", "id_kron_sparse", "dense", "dense_kron_id", "id_kron_dense", "dataterm_sublabel", "conv2d",
-          "sym_gradient2d", "diags", "zero"]
+          "sym_gradient2d", "conv2d_strided", "radon2d", "sample2d", "fft2d", "wavelet2d", "tensor_gradient2d", "diags", "zero"]
 PLACEMENTS = ["alone", "below", "right"]
 # kept as text: a CSR and a pattern-compressed sparse block and a Kronecker block (the classes with two sides), the second at offset pointers
 FULL_TEXT = ["sparse.random5x7.f32 alone", "sparse.difference300.f32 alone", "id_kron_sparse.f64 below"]
 # blocks with a guard, and its text
 GUARDS = {"sparse": "BlockSparse", "sparse_kron_id": "BlockKronSparse", "id_kron_sparse": "BlockKronSparse", "dense": "BlockDense", "dense_kron_id": "BlockKronDense",
-          "id_kron_dense": "BlockKronDense", "dataterm_sublabel": "BlockDatatermSublabel", "conv2d": "BlockConv2D", "diags": "BlockDiags"}
+          "id_kron_dense": "BlockKronDense", "dataterm_sublabel": "BlockDatatermSublabel", "conv2d": "BlockConv2D", "conv2d_strided": "BlockConv2DStrided", "radon2d": "BlockRadon2D",
+          "sample2d": "BlockSample2D", "fft2d": "BlockFFT2D", "wavelet2d": "BlockWavelet2D", "tensor_gradient2d": "BlockTensorGradient2D", "diags": "BlockDiags"}
 
 
 def _split(text):
@@ -112,7 +117,8 @@ def test_every_block_is_pinned_in_both_precisions_and_reaches_its_entry_points(t
     for t in ("f32", "f64"):
         for entry in ("grad2d_fwd", "grad2d_adj", "grad3d_fwd", "grad3d_adj", "csr_spmv", "csr_spmv_acc", "pattern_spmv", "pattern_spmv_anchored", "sparse_kron_id",
                       "sparse_kron_id_acc", "id_kron_sparse", "id_kron_sparse_acc", "dense_gemv", "dense_gemv_acc", "dense_kron_id", "dense_kron_id_acc", "id_kron_dense",
-                      "id_kron_dense_acc", "linop_dataterm_sublabel", "conv2d", "linop_sym_gradient2d", "diags_fwd", "diags_adj", "scale", "negate"):
+                      "id_kron_dense_acc", "linop_dataterm_sublabel", "conv2d", "linop_sym_gradient2d", "conv2d_strided", "radon2d", "sample2d", "fft2d", "wavelet2d",
+                      "linop_tensor_gradient2d", "diags_fwd", "diags_adj", "scale", "negate"):
             assert "%s_%s" % (entry, t) in calls, (entry, t)
     # the sparse matrices take the paths they are named for, in both directions
     for t in ("f32", "f64"):
