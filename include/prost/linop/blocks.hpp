@@ -11,6 +11,7 @@
 #include "prost/linop/sample2d.hpp"
 #include "prost/linop/sym_gradient2d.hpp"
 #include "prost/linop/tensor_gradient2d.hpp"
+#include "prost/linop/nonlocal_gradient2d.hpp"
 #include "prost/linop/wavelet2d.hpp"
 
 namespace prost {
@@ -450,6 +451,38 @@ class BlockTensorGradient2D : public ProductBlock<T> {
   int mode_;
   std::vector<T> tensor_;          ///< rounded once to T
   device_vector<T> d_tensor_;
+};
+
+/// the nonlocal gradient (K u)_m[p] = w_m(p) (u[p + d_m] - u[p]) on L channels of an ny x nx grid, without a matrix: M displacements
+/// inside a window of reach 15 and one weight plane per displacement, shared by all channels (nonlocal TV, nonlocal Huber / TV-L1).
+/// M L N rows (plane (m, c) at (m L + c) N) by L N columns.  Arithmetic, sums and error bound: prost/linop/nonlocal_gradient2d.hpp.  No
+/// describe(): the block runs on the generic paths.  Stored on the device: the M weight planes, N values each; the displacements
+/// travel with every launch.
+template <typename T>
+class BlockNonlocalGradient2D : public ProductBlock<T> {
+ public:
+  /// checks every argument (messages start with "BlockNonlocalGradient2D: "); offsets: M pairs (dy, dx) one after the other; weights: M
+  /// planes of nx ny values one after the other; declared_rows / declared_cols < 0: no size was declared
+  static BlockNonlocalGradient2D<T>* Create(size_t row, size_t col, double nx, double ny, double L, const std::vector<double>& offsets,
+                                            const std::vector<double>& weights, double declared_rows = -1, double declared_cols = -1);
+  virtual void Initialize();
+  virtual void Release();
+  virtual T row_sum(size_t row, T alpha) const;
+  virtual T col_sum(size_t col, T alpha) const;
+  virtual void row_sums(T* out, T alpha) const;              ///< one pass over the pixels
+  virtual void col_sums(T* out, T alpha) const;
+  virtual size_t gpu_mem_amount() const { return weights_.size() * sizeof(T); }
+
+ protected:
+  BlockNonlocalGradient2D(size_t row, size_t col, size_t nx, size_t ny, size_t L, int M)
+      : ProductBlock<T>(row, col, (size_t)M * L * nx * ny, L * nx * ny), nx_(nx), ny_(ny), L_(L), M_(M) {}
+  virtual void Product(T* res, const T* rhs, bool transpose, bool accumulate);
+  size_t nx_, ny_, L_;
+  int M_;
+  nonlocal_gradient2d::Offsets offsets_;
+  std::vector<signed char> pairs_;  ///< (dy, dx) pairs as the entry points take them
+  std::vector<T> weights_;          ///< rounded once to T
+  device_vector<T> d_weights_;
 };
 
 /// constant-coefficient multi-diagonal block; `identity` maps here (block_diags.hpp, identity.m:11-12)

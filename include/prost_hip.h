@@ -401,6 +401,24 @@ int prost_hip_linop_sym_gradient2d_f64(double* res, const double* rhs, size_t nx
  * 2^53.  The values of the tensor are the caller's: BlockTensorGradient2D refuses non-finite ones before it uploads them. */
 int prost_hip_linop_tensor_gradient2d_f32(float* res, const float* rhs, const float* tensor, size_t nx, size_t ny, size_t L, int mode, int transpose, int accumulate, void* stream);
 int prost_hip_linop_tensor_gradient2d_f64(double* res, const double* rhs, const double* tensor, size_t nx, size_t ny, size_t L, int mode, int transpose, int accumulate, void* stream);
+/* BlockNonlocalGradient2D (additions; ABI version unchanged; kernels_linop_nonlocal_gradient2d.hip, arithmetic and order of operations:
+ * prost/linop/nonlocal_gradient2d.hpp): the nonlocal gradient (K u)_m[p] = w_m(p) (u[p + d_m] - u[p]) on L channels of an ny x nx grid,
+ * N = nx ny, pixel (y, x) at p = y + x ny.  Domain, L N values: u_c[p] at c N + p.  Range, M L N values, displacement-major: plane
+ * (m, c) at (m L + c) N + p.  offsets: a HOST pointer to M pairs (dy_m, dx_m) of int8, read before the call returns (they travel to the
+ * kernels as an argument); 1 <= M <= 64, |dy|, |dx| <= 15, no (0, 0).  weights: a DEVICE pointer to M planes of N values shared by all
+ * channels, w_m[p] at m N + p.  Term m is present at p iff (y + dy_m, x + dx_m) lies in the grid; a masked term is selected away, never
+ * formed, so a weight whose target is outside the grid reaches no output.  Every difference, product and addition is rounded once:
+ *   transpose == 0:  res[(m L + c) N + p] = present ? w_m[p] (u_c[p + dy_m + dx_m ny] - u_c[p]) : +0
+ *   transpose != 0:  res[c N + p] = s, with s = +0 and, for m ascending, s = s - w_m[p] y_{m,c}[p] where term m is present at p, then
+ *                    s = s + w_m[p'] y_{m,c}[p'] where p' = (y - dy_m, x - dx_m) lies in the grid
+ * accumulate != 0 stores res + value, added last.  With offsets ((0, 1), (1, 0)) and weights 1 the forward product gives the bits of
+ * prost_hip_grad2d_fwd.  Any alignment of T is accepted (16-byte aligned res, rhs and weights and a height that is a multiple of
+ * 16 / sizeof(T) take the vector kernels; the bits are the same).  Aliasing: res must NOT overlap rhs or the weights.  No atomics: a call
+ * repeats its bits.  No allocation, copy or synchronisation.  Refused without a launch: nx, ny or L of 0, M outside 1 .. 64, an offset
+ * beyond 15 or (0, 0), null pointers, M L N beyond 2^53, more than 2^31 - 1 workgroups (tiles of 64 x 16 pixels times channel passes).
+ * Duplicate offsets are not looked for, and the values of the weights are the caller's: BlockNonlocalGradient2D refuses both. */
+int prost_hip_linop_nonlocal_gradient2d_f32(float* res, const float* rhs, const float* weights, size_t nx, size_t ny, size_t L, int M, const signed char* offsets, int transpose, int accumulate, void* stream);
+int prost_hip_linop_nonlocal_gradient2d_f64(double* res, const double* rhs, const double* weights, size_t nx, size_t ny, size_t L, int M, const signed char* offsets, int transpose, int accumulate, void* stream);
 /* x = beta * x (beta == 0 -> zero fill): thrust::fill / transform at linearoperator.cu:140-147 */
 /* x[i] = value (thrust::fill, linearoperator.cu:140-147; also used for preconditioners that are one constant: the
  * gradient blocks' row / column sums are, block_gradient2d.cu:154-163, so nothing is uploaded for them) */

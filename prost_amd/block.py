@@ -511,6 +511,77 @@ def tensor_gradient2d(nx, ny, L, tensor):
     return lambda row, col, nrows, ncols: [["tensor_gradient2d", row, col, data], sz]
 
 
+NONLOCAL_GRADIENT2D_MAX_SIZE = 2 ** 53     # sizes travel as doubles
+NONLOCAL_GRADIENT2D_MAX_OFFSETS = 64
+NONLOCAL_GRADIENT2D_MAX_REACH = 15         # the reach of conv2d's 31 x 31 window
+
+
+def nonlocal_window(radius):
+    """The offsets (dy, dx) of the full (2 r + 1)^2 - 1 window of radius r, an (M, 2) integer array: dx ascending from -r to r and, for
+    each dx, dy ascending from -r to r, (0, 0) left out -- the column-major order of the window's pixels.  nonlocal_window(1) is
+    (-1,-1), (0,-1), (1,-1), (-1,0), (1,0), (-1,1), (0,1), (1,1)."""
+    r = _integer("nonlocal_window", "radius", radius, NONLOCAL_GRADIENT2D_MAX_REACH)
+    return np.array([(dy, dx) for dx in range(-r, r + 1) for dy in range(-r, r + 1) if (dy, dx) != (0, 0)], dtype=np.int64)
+
+
+def nonlocal_gradient2d(nx, ny, L, offsets, weights):
+    """The nonlocal gradient (K u)_m[p] = w_m(p) (u[p + d_m] - u[p]) on L channels of an ny x nx grid, applied without a matrix: the
+    operator of nonlocal TV denoising and inpainting (Gilboa-Osher) and of the nonlocal Huber / TV-L1 regularisers of flow and depth.
+    N = nx ny, pixel (y, x) at p = y + x ny.  Domain, L N values: u_c[p] at c N + p.  Range, M L N values, displacement-major like the
+    gx / gy planes of gradient2d: plane (m, c) at (m L + c) N + p, so sum_norm2(M L, False, ..) or sum_norm2(M, False, ..) group per pixel.
+    offsets: an (M, 2) integer array of displacements (dy, dx), 1 <= M <= 64, pairwise distinct, not (0, 0), |dy|, |dx| <= 15
+    (nonlocal_window(r) gives a full window).  weights: one plane per displacement, shared by all channels and rounded once to the
+    precision of the problem -- an (M, N) array, an (M, ny, nx) array w[m, y, x] (each plane is flattened with y fastest), or a sequence
+    of M planes, each a vector of N values or an (ny, nx) array.  Zeros and negative values are legal; non-finite values are refused.
+    A term whose target p + d_m lies outside the grid is absent: it has no row entry, and its weight reaches no output.  With offsets
+    ((0, 1), (1, 0)) and weights 1 the forward product is gradient2d bit for bit.  The device stores the M N weights and nothing per
+    channel; the sparse matrix of the same operator stores 2 M entries with their indices per pixel and channel, once for each side."""
+    name = "nonlocal_gradient2d"
+    nx, ny, L = [_integer(name, what, v) for what, v in (("nx", nx), ("ny", ny), ("L", L))]
+    N = nx * ny
+    off = _numbers(name, offsets, "the offsets have to be an array of numbers")
+    if off.ndim != 2 or off.shape[1] != 2:
+        raise ValueError("%s: the offsets have shape %r; they are an (M, 2) array of (dy, dx)" % (name, off.shape))
+    M = off.shape[0]
+    if M < 1 or M > NONLOCAL_GRADIENT2D_MAX_OFFSETS:
+        raise ValueError("%s: M = %d offsets; M has to be 1 .. %d" % (name, M, NONLOCAL_GRADIENT2D_MAX_OFFSETS))
+    if not np.isfinite(off).all() or np.any(off != np.floor(off)):
+        raise ValueError("%s: the offsets have to be integers" % name)
+    off = off.astype(np.int64)
+    if np.any(np.all(off == 0, axis=1)):
+        raise ValueError("%s: offset %d is (0, 0), which is no displacement" % (name, int(np.flatnonzero(np.all(off == 0, axis=1))[0])))
+    if len({(int(dy), int(dx)) for dy, dx in off}) != M:
+        raise ValueError("%s: the offsets have to be pairwise distinct" % name)
+    if np.abs(off).max() > NONLOCAL_GRADIENT2D_MAX_REACH:
+        raise ValueError("%s: an offset reaches beyond %d" % (name, NONLOCAL_GRADIENT2D_MAX_REACH))
+    if M * L * N > NONLOCAL_GRADIENT2D_MAX_SIZE:
+        raise ValueError("%s: M L nx ny = %d rows; the size has to stay within 2^53" % (name, M * L * N))
+
+    def plane(v, what):
+        v = _numbers(name, v, "%s has to be an array of numbers" % what)
+        if v.ndim == 2 and v.shape == (ny, nx):
+            v = v.reshape(-1, order="F")                   # p = y + x ny
+        if v.ndim != 1 or v.size != N:
+            raise ValueError("%s: %s has shape %r; a plane is a vector of nx ny = %d values or an (ny, nx) = (%d, %d) array" % (name, what, v.shape, N, ny, nx))
+        return v
+
+    if isinstance(weights, (list, tuple)) and len(weights) > 0 and not np.isscalar(weights[0]):
+        planes = [plane(v, "plane %d of the weights" % i) for i, v in enumerate(weights)]
+    else:
+        w = _numbers(name, weights, "the weights have to be an array of numbers")
+        if w.ndim not in (2, 3):
+            raise ValueError("%s: the weights have shape %r; they are an (M, N) or (M, ny, nx) array or a sequence of M planes" % (name, w.shape))
+        planes = [plane(v, "plane %d of the weights" % i) for i, v in enumerate(w)]
+    if len(planes) != M:
+        raise ValueError("%s: %d planes of weights for M = %d offsets" % (name, len(planes), M))
+    flat = np.concatenate(planes)
+    if not np.isfinite(flat).all():
+        raise ValueError("%s: the weights hold a non-finite value" % name)
+    sz = [M * L * N, L * N]
+    data = [nx, ny, L, off.reshape(-1).astype(np.float64), flat]
+    return lambda row, col, nrows, ncols: [[name, row, col, data], sz]
+
+
 def diags(nrows, ncols, factors, offsets):
     sz = [nrows, ncols]
     data = [nrows, ncols, np.atleast_1d(np.asarray(factors, dtype=np.float64)),

@@ -505,6 +505,13 @@ std::map<std::string, typename Factory<T>::BlockFactory>& Factory<T>::block_reg(
       return BlockTensorGradient2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), GetScalarFromCell(d, 3), tensor, size.first,
                                               size.second);
     };
+    // the nonlocal gradient: cells { nx, ny, L, offsets (full vector: M pairs dy, dx), weights (full vector: M planes of nx ny values) }
+    reg["nonlocal_gradient2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
+      const auto size = declared_size(d, 5, "BlockNonlocalGradient2D: the data cells are { nx, ny, L, offsets, weights } or { nx, ny, L, offsets, weights, nrows, ncols }.");
+      const std::vector<double> offsets = full_vector(d, 3, "BlockNonlocalGradient2D: the offsets have to be a full vector of type single or double.");
+      const std::vector<double> weights = full_vector(d, 4, "BlockNonlocalGradient2D: the weights have to be a full vector of type single or double.");
+      return BlockNonlocalGradient2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), offsets, weights, size.first, size.second);
+    };
     // the dense blocks (factory.cpp:590-601, :694-716): cell 0 is a full matrix, column-major, converted to T.  A sparse cell is refused:
     // the reference would read its value array as if it were the full matrix.
     auto dense_data = [](const prost_value* pm) {

@@ -1011,6 +1011,74 @@ void BlockTensorGradient2D<T>::Product(T* r, const T* x, bool transpose, bool ac
 template class BlockTensorGradient2D<float>;
 template class BlockTensorGradient2D<double>;
 
+// ---- the nonlocal gradient w_m(p) (u[p + d_m] - u[p]): M displacements, one weight plane each, without a matrix ----
+template <typename T>
+BlockNonlocalGradient2D<T>* BlockNonlocalGradient2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, const std::vector<double>& offsets,
+                                                               const std::vector<double>& weights, double declared_rows, double declared_cols) {
+  const char* kName = "BlockNonlocalGradient2D";
+  namespace nl = nonlocal_gradient2d;
+  CheckIntegers(kName, {{"nx", nx}, {"ny", ny}, {"L", L}}, kTwo53, " has to be a positive integer.");
+  if (offsets.empty() || offsets.size() % 2 != 0 || offsets.size() / 2 > (size_t)nl::kMaxOffsets)
+    Refuse(kName, "the offsets hold ", offsets.size(), " values; they are M pairs (dy, dx), M from 1 to ", nl::kMaxOffsets, ".");
+  CheckFinite(kName, offsets, "the offsets hold");
+  const size_t M = offsets.size() / 2;
+  for (size_t m = 0; m < M; m++) {
+    const double dy = offsets[2 * m], dx = offsets[2 * m + 1];
+    if (dy != std::floor(dy) || dx != std::floor(dx)) Refuse(kName, "offset ", m, " = (", dy, ", ", dx, ") is not a pair of integers.");
+    if (std::fabs(dy) > nl::kMaxReach || std::fabs(dx) > nl::kMaxReach) Refuse(kName, "offset ", m, " = (", dy, ", ", dx, ") reaches beyond ", nl::kMaxReach, ".");
+    if (dy == 0 && dx == 0) Refuse(kName, "offset ", m, " is (0, 0), which is no displacement.");
+    for (size_t k = 0; k < m; k++)
+      if (offsets[2 * k] == dy && offsets[2 * k + 1] == dx) Refuse(kName, "offsets ", k, " and ", m, " are both (", dy, ", ", dx, "); the offsets have to be distinct.");
+  }
+  const double rows = (double)M * L * nx * ny, cols = L * nx * ny;
+  if (!((double)M * L * (nx * ny) <= kTwo53) || !(nx * ny <= kTwo53)) Refuse(kName, "M L nx ny = ", rows, " rows; the size has to stay within 2^53.");
+  if ((double)weights.size() != (double)M * nx * ny) Refuse(kName, "the weights hold ", weights.size(), " values, not M = ", M, " planes of nx ny = ", nx * ny, ".");
+  const double tiles = std::ceil(ny / nl::kTileY) * std::ceil(nx / nl::kTileX) * L;        // at least one channel per pass
+  if (!(tiles < kTwo31)) Refuse(kName, "a grid of ", ny, " x ", nx, " with ", L, " channels needs up to ", tiles, " workgroups; it has to stay below 2^31.");
+  CheckDeclaredSize(kName, declared_rows, declared_cols, rows, cols, "M L nx ny x L nx ny");
+  std::unique_ptr<BlockNonlocalGradient2D<T>> b(new BlockNonlocalGradient2D<T>(row, col, (size_t)nx, (size_t)ny, (size_t)L, (int)M));
+  b->offsets_ = nl::Offsets();
+  b->pairs_.resize(2 * M);
+  for (size_t m = 0; m < M; m++) {
+    b->offsets_.dy[m] = b->pairs_[2 * m] = (signed char)offsets[2 * m];
+    b->offsets_.dx[m] = b->pairs_[2 * m + 1] = (signed char)offsets[2 * m + 1];
+  }
+  b->weights_.resize(weights.size());
+  for (size_t i = 0; i < weights.size(); i++) {
+    const T w = (T)weights[i];                      // rounded once
+    if (!std::isfinite((double)w))
+      Refuse(kName, "value ", i % (size_t)(nx * ny), " of plane ", i / (size_t)(nx * ny), " of the weights, ", weights[i], ", is not finite", PrecisionStop<T>());
+    b->weights_[i] = w;
+  }
+  return b.release();
+}
+template <typename T>
+void BlockNonlocalGradient2D<T>::Initialize() { d_weights_ = weights_; }
+template <typename T>
+void BlockNonlocalGradient2D<T>::Release() { d_weights_.clear(); }
+template <typename T>
+T BlockNonlocalGradient2D<T>::row_sum(size_t row, T alpha) const { return (T)nonlocal_gradient2d::RowSum(row, weights_.data(), offsets_, nx_, ny_, L_, (double)alpha); }
+template <typename T>
+T BlockNonlocalGradient2D<T>::col_sum(size_t col, T alpha) const { return (T)nonlocal_gradient2d::ColSum(col, weights_.data(), offsets_, M_, nx_, ny_, (double)alpha); }
+template <typename T>
+void BlockNonlocalGradient2D<T>::row_sums(T* out, T alpha) const {
+  const size_t N = nx_ * ny_;
+  for (int m = 0; m < M_; m++)                      // the L planes of displacement m are the same
+    AddPlaneSums(out + (size_t)m * L_ * N, N, L_, [&](size_t p) { return nonlocal_gradient2d::PixelRowSum(weights_.data(), offsets_, m, nx_, ny_, p, (double)alpha); });
+}
+template <typename T>
+void BlockNonlocalGradient2D<T>::col_sums(T* out, T alpha) const {
+  AddPlaneSums(out, nx_ * ny_, L_, [&](size_t p) { return nonlocal_gradient2d::PixelColSum(weights_.data(), offsets_, M_, nx_, ny_, p, (double)alpha); });
+}
+template <typename T>
+void BlockNonlocalGradient2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
+  if (d_weights_.size() != weights_.size()) throw Exception("BlockNonlocalGradient2D used before Initialize().");
+  CheckHip(Api<T>::linop_nonlocal_gradient2d(r, x, d_weights_.data(), nx_, ny_, L_, M_, pairs_.data(), transpose ? 1 : 0, acc ? 1 : 0, CurrentStream()),
+           "linop_nonlocal_gradient2d");
+}
+template class BlockNonlocalGradient2D<float>;
+template class BlockNonlocalGradient2D<double>;
+
 // ---- diags block ----
 static bool g_diags_quirk = false;
 template <typename T> void BlockDiags<T>::SetReferenceGridQuirk(bool on) { g_diags_quirk = on; }
