@@ -38,7 +38,7 @@ __device__ __forceinline__ void static_for(F&& f) {
 // one launch of the level-per-wavefront family (kernels_fused_iterk_lw.hip; K = 3 and 4): the instance for (g_fn, per-pixel b), or,
 // with `place` set, the K = 4 / square / per-pixel-b instance that records where its waves ran.  Returns 0 or the error code of `fail`.
 template <int K>
-int launch_iterk_levelwave(int g_fn, bool b_per_pixel, dim3 grid, hipStream_t s, float* x_out, float* y_out, const float* x, const float* y,
+int launch_iterk_levelwave(int g_fn, bool b_per_pixel, int ring, dim3 grid, hipStream_t s, float* x_out, float* y_out, const float* x, const float* y,
                            const FusedArgs<float>& a, const StepsK<K>& sp, const PdhgRecord<float>* rec, unsigned* place);
 
 }  // namespace prost_hip

@@ -37,6 +37,16 @@ PH_LW_HD constexpr bool lw_d_active(int K, int xa, int xb, int nx, int l, int q)
 // columns of the iterate (level 0) a chunk loads through the ring; y_1^0 at column xa - K goes into registers directly
 PH_LW_HD constexpr bool lw_loaded(int K, int xa, int xb, int nx, int k) { return k >= 0 && k < nx && k >= xa - K + 1 && k <= xb + K - 1; }
 PH_LW_HD constexpr int lw_ring_slot(int k) { return (int)((unsigned)(k + 4 * kLevelWaveRing) % (unsigned)kLevelWaveRing); }      // k >= -K > -4 R
+// The same ring with R slots (R = 2: the K = 4 per-pixel-b instances, whose workgroup then holds 32 KiB and five fit a CU).  Wave 1
+// keeps R - 1 batches in flight: the prologue issues the columns p0 .. p0 + R - 2, the step of column p issues column p + R - 1 into
+// the slot of column p - 1 -- read, and waited for, one barrier ago -- and then waits for column p with lw_ring_wait() batches behind it.
+PH_LW_HD constexpr int lw_ring_slot(int k, int R) { return (int)((unsigned)(k + 4 * R) % (unsigned)R); }      // k >= -K >= -4 >= -4 R + 4
+// batches issued behind column p's when its step waits: the columns p + 1 .. p + R - 1 that are loaded (the loaded columns are one range)
+PH_LW_HD constexpr int lw_ring_wait(int K, int xa, int xb, int nx, int p, int R) {
+  int n = 0;
+  for (int r = 1; r < R; r++) n += lw_loaded(K, xa, xb, nx, p + r) ? 1 : 0;
+  return n;
+}
 
 // link slots: a wave writes lw_slot_written(t) at the end of step t and reads lw_slot_read(t) at its start (t >= 1; step 0 reads nothing)
 PH_LW_HD constexpr int lw_slot_written(int t) { return t & 1; }
@@ -48,6 +58,13 @@ PH_LW_HD constexpr bool lw_stores_y(int xa, int xb, int q) { return q >= xa && q
 
 // bytes of LDS per workgroup: (K - 1) links x 2 slots + the ring, planes of 1 KiB (y_1, y_2, x and, per pixel, b)
 PH_LW_HD constexpr int lw_lds_bytes(int K, int planes) { return (2 * (K - 1) + kLevelWaveRing) * planes * 1024; }
+PH_LW_HD constexpr int lw_lds_bytes(int K, int planes, int R) { return (2 * (K - 1) + R) * planes * 1024; }
+// the ring depth of an instance and the workgroups of it a CU can hold -- the kernel's launch bounds (160 KiB of LDS; the register
+// budget of the instances allows five wavefronts per SIMD): K = 4 with per-pixel b runs two slots, 32 KiB, five per CU; every other
+// instance keeps three slots.  The chunk rule below counts four per CU for all of them: a grid cut for five is slower.
+PH_LW_HD constexpr int lw_ring_depth(int K, bool b_per_pixel) { return K == 4 && b_per_pixel ? 2 : kLevelWaveRing; }
+PH_LW_HD constexpr int lw_groups_per_cu(int R) { return R == 2 ? 5 : 4; }
+constexpr int kLevelWaveCUs = 256;          // slots of a round: kLevelWaveCUs x the workgroups per CU the rule counts (4: 1024)
 
 // the shortest chunk in [lo, hi] whose workgroups (strips x chunks) all run in one round of `slots` resident workgroups; hi where
 // none does (such images run several rounds whatever the length).  A chunk of c columns runs c + 3K - 2 steps: shorter is cheaper.

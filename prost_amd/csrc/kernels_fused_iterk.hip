@@ -342,10 +342,11 @@ __global__ void __launch_bounds__(kWave, WAVES)
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-static bool iterk_shape_ok(const prost_hip_fused_desc* d, int dtype) {
+// min_nx: the single-wave pipeline needs 8 columns; the level-wave family's index rules (iterk_levelwave.hpp) hold from 2
+static bool iterk_shape_ok(const prost_hip_fused_desc* d, int dtype, size_t min_nx = 8) {
   if (!d || dtype != 0 || (d->arith != PROST_HIP_ARITH_FMAD && d->arith != PROST_HIP_ARITH_EXACT)) return false;
   if (d->is3d || d->L != 1 || d->var_T || d->f_moreau || d->g_b_masked) return false;
-  if (d->nx < 8 || d->ny < 8 || d->ny % 4 != 0) return false;
+  if (d->nx < min_nx || d->ny < 8 || d->ny % 4 != 0) return false;
   if ((double)d->nx * (double)d->ny * 4 >= 4294967296.0) return false;
   if ((d->g_fn != PROST_FN_SQUARE && d->g_fn != PROST_FN_ABS) || d->f_fn != PROST_FN_IND_LEQ0) return false;
   for (int k = 0; k < 7; k++) {
@@ -390,12 +391,23 @@ static unsigned* iterk_place_record(void* ws) {
   return p && p[0] == '1' && p[1] == 0 ? static_cast<unsigned*>(ws) : nullptr;
 }
 
+// the depth of the level-wave instance's input ring: lw_ring_depth, or three slots for every instance with PROST_ITERK_LW_RING=3 (read per
+// launch, like PROST_ITERK_LEVELWAVE: the tests and tools/iterk_levelwave_probe.py run both depths in one process)
+static int iterk_levelwave_ring(const prost_hip_fused_desc* d, int K) {
+  const char* e = getenv("PROST_ITERK_LW_RING");
+  return e && e[0] == '3' && e[1] == 0 ? kLevelWaveRing : lw_ring_depth(K, d->g_coeff_ptr[1] != nullptr);
+}
+
 static int iterk_chunk_cols(const prost_hip_fused_desc* d, int K, bool res, int cols) {
   const size_t rpw = (size_t)iterk_rows_per_wave(K), strips = (d->ny + rpw - 1) / rpw;
   if (cols <= 0 && iterk_levelwave(d, K, res)) {
-    // a workgroup of K wavefronts holds 28 (K = 3) / 36 KiB (K = 4) of LDS: four per CU, 1024 on the chip, four wavefronts per SIMD.
-    // The shortest chunk whose workgroups all run in one round of four per CU (4096^2: 69 columns, 1020 workgroups); a chunk of c
-    // columns runs c + 3K - 2 steps, so short chunks pay more for the skew than the single-wave pipeline does.
+    // a workgroup of K wavefronts holds up to 28 (K = 3) / 36 KiB (K = 4) of LDS: its round is four per CU, 1024 on the chip, four
+    // wavefronts per SIMD.  The shortest chunk whose workgroups all run in one such round (4096^2: 69 columns, 1020 workgroups); a
+    // chunk of c columns runs c + 3K - 2 steps, so short chunks pay more for the skew than the single-wave pipeline does.
+    // K = 4 with per-pixel b (two ring slots, 32 KiB) does fit five per CU, and the hardware places five (1275 workgroups of 55 columns at
+    // 4096^2: 247 CUs hold five) -- but a step with five wavefronts per SIMD takes a quarter longer, and the round of five is slower
+    // than the round of four at every size measured: 4096^2 +2.9 %, 3072^2 +4.7 %, 2048^2 +10.8 % (docs/rounds/r31.md).  So the rule
+    // counts four per CU for every instance.
     cols = lw_one_round_cols((long long)d->nx, (long long)strips);
     static const char* const names[] = {"", "", "", "PROST_ITERK3_COLS", "PROST_ITERK4_COLS"};
     return iterk_override(names[K], cols);
@@ -421,7 +433,10 @@ static int iterk_chunk_cols(const prost_hip_fused_desc* d, int K, bool res, int 
 template <int K>
 static int run_iterk(const prost_hip_fused_desc* d, float* x_out, float* y_out, const float* x, const float* y, const double* tau, const double* sigma,
                      const double* theta, int cols, double* out4, void* ws, void* stream, void* record, const RuleTail* tail) {
-  if (!iterk_shape_ok(d, 0) || !aligned16(x_out) || !aligned16(y_out) || !aligned16(x) || !aligned16(y)) {
+  // (a direct launch of the level-wave family takes images from two columns; prost_hip_fused_iterationk_max, which the solver's launch
+  // plan asks, keeps answering 0 below eight)
+  const bool narrow_ok = d && d->arith == PROST_HIP_ARITH_EXACT && d->nx >= 2 && iterk_levelwave(d, K, out4 != nullptr);
+  if (!iterk_shape_ok(d, 0, narrow_ok ? 2 : 8) || !aligned16(x_out) || !aligned16(y_out) || !aligned16(x) || !aligned16(y)) {
     set_error("fused K-iteration launch: unsupported description"); return 1;
   }
   if (out4 && !ws) { set_error("fused K-iteration launch: residuals need the reduction workspace"); return 1; }
@@ -453,7 +468,7 @@ static int run_iterk(const prost_hip_fused_desc* d, float* x_out, float* y_out, 
       const bool bpw = d->g_coeff_ptr[1] != nullptr;
       unsigned* const place = iterk_place_record(ws);
       if (place && !(K == 4 && d->g_fn == PROST_FN_SQUARE && bpw)) { set_error("fused K-iteration launch: the placement record exists for K = 4, square, per-pixel b"); return 1; }
-      return launch_iterk_levelwave<K>(d->g_fn, bpw, grid, s, x_out, y_out, x, y, a, sp, rec, place);
+      return launch_iterk_levelwave<K>(d->g_fn, bpw, iterk_levelwave_ring(d, K), grid, s, x_out, y_out, x, y, a, sp, rec, place);
     }
   }
   constexpr int R = IterKGeom<K>::R, W = IterKGeom<K>::W;

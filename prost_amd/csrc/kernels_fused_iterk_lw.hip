@@ -17,20 +17,26 @@ namespace prost_hip {
 // it).  A wave reads link slot (t - 1) & 1 and writes slot t & 1, so the only writer of a slot and its only reader are always
 // separated by a barrier in both directions.  Every wave of a workgroup runs lw_steps() steps whatever its level, rows or columns;
 // the only return (rec->stop) is uniform and lies in front of the first barrier.
-// Loads: wave 1 alone issues the input ring (R = 3 columns, the batch of column p + 2 in front of the wait for column p) and reads
+// Loads: wave 1 alone issues the input ring (R columns, the batch of column p + R - 1 in front of the wait for column p) and reads
 // it; it stores nothing, so its vmcnt counts load batches only.  Wave K alone stores.
+// Ring depth R (lw_ring_depth): three slots, except K = 4 with per-pixel b, which runs two: (6 + 2) x 4 KiB = 32 KiB per workgroup.  With
+// two slots one batch is in flight while a column is computed: the batch of column p + 1 goes into the slot of column p - 1, whose
+// ds_read_b128 were waited for (lgkmcnt(0)) one barrier ago.  That is 1.4 % of a launch faster than three slots at the same chunk
+// length.  Five such workgroups fit a CU (the launch bounds allow it, the hardware places them), but a grid cut for five per CU is
+// slower than one cut for four, so the chunk rule does not use it (docs/rounds/r31.md).  PROST_ITERK_LW_RING=3 keeps three slots.
 //
 // Placement (measured, docs/rounds/r26.md): workgroups b, b + 256, b + 512, b + 768 share a CU, and the hardware starts each of them
 // on the next SIMD, so with level = wave + 1 every SIMD already holds one wave of each level: the levels' idle steps (2 (l - 1) at the
 // start, 2 (K - l) at the end), wave 1's loads and wave K's stores are spread over the four SIMDs.  Rotating the levels by b / 256
 // undoes exactly that (one level per SIMD) and costs 5.7 % of a launch at 4096^2, so the assignment stays as it is.
 // PLACE (tools/iterk_levelwave_probe.py only): lane 0 of every wave records where it ran, after its last step, in place[b K + wave].
-template <int K, int GFN, bool BPTR, bool PLACE = false>
-__global__ void __launch_bounds__(K * kWave, 4)
+template <int K, int GFN, bool BPTR, int R = kLevelWaveRing, bool PLACE = false>
+__global__ void __launch_bounds__(K * kWave, lw_groups_per_cu(R))
     fused_iter2d_xkw_kernel(float* __restrict__ x_out, float* __restrict__ y_out, const float* __restrict__ x, const float* __restrict__ y,
                             FusedArgs<float> a, const StepsK<K> sp, const PdhgRecord<float>* __restrict__ rec, unsigned* __restrict__ place) {
   static_assert(K >= 2 && K <= 4, "one halo lane per side: K <= 4");
-  constexpr int VEC = 4, H = 1, R = kLevelWaveRing;
+  static_assert(R == 2 || R == 3, "the counted waits of wave 1 are written for two and three slots");
+  constexpr int VEC = 4, H = 1;
   typedef float T;
   typedef native_f4 V4;
   if (rec && rec->stop) return;
@@ -56,7 +62,7 @@ __global__ void __launch_bounds__(K * kWave, 4)
   constexpr int NB = 3 + (BPTR ? 1 : 0);
   constexpr int kSlot = NB * 1024;                 // one column: planes y_1, y_2, x (, b) of 64 lanes x 16 bytes
   // [ring: R slots][link 1: 2 slots] .. [link K - 1: 2 slots]; link l is written by wave l and read by wave l + 1
-  __shared__ __attribute__((aligned(16))) char lds[lw_lds_bytes(K, NB)];
+  __shared__ __attribute__((aligned(16))) char lds[lw_lds_bytes(K, NB, R)];
   const T* const y2base = y + N;
   T* const y2out = y_out + N;
   const T* const bptr = BPTR ? a.g_ptr[1] : nullptr;
@@ -68,7 +74,7 @@ __global__ void __launch_bounds__(K * kWave, 4)
   auto ring_issue = [&](idx_t k) {
     if (active) {
       const unsigned o = off_of(k);
-      char* slot = lds + lw_ring_slot(k) * kSlot;
+      char* slot = lds + lw_ring_slot(k, R) * kSlot;
       __builtin_amdgcn_global_load_lds((glb_void_k*)(reinterpret_cast<const char*>(y) + o), (lds_void_k*)(slot), 16, 0, ITERK_LOAD_AUX);
       __builtin_amdgcn_global_load_lds((glb_void_k*)(reinterpret_cast<const char*>(y2base) + o), (lds_void_k*)(slot + 1024), 16, 0, ITERK_LOAD_AUX);
       __builtin_amdgcn_global_load_lds((glb_void_k*)(reinterpret_cast<const char*>(x) + o), (lds_void_k*)(slot + 2048), 16, 0, ITERK_LOAD_AUX);
@@ -90,6 +96,9 @@ __global__ void __launch_bounds__(K * kWave, 4)
   // between a read, the arithmetic and a write.  Left to itself the SLP vectoriser packs the scalar lambdas of the single-wave kernel
   // too, but into pairs of its own choosing (row 1 of one array with row 3 of another) that it assembles with two v_mov_b32
   // per operand: 44 of that step's 243 VALU instructions were such copies (docs/rounds/r28.md).
+  // The file is built with packed fp32 instructions switched off (Makefile): a pair operation is then two plain instructions on the
+  // halves of the pair, in place -- the layout and the absence of copies are what the pairs are for, the v_pk_* forms cost VALU time
+  // (docs/rounds/r31.md).
   typedef native_f2 V2;
   auto quad = [](const V2 (&v)[2]) { return __builtin_shufflevector(v[0], v[1], 0, 1, 2, 3); };
   auto column_write = [&](unsigned slot_off, const V2 (&v0)[2], const V2 (&v1)[2], const V2 (&v2)[2], const V2 (&v3)[2]) {
@@ -185,7 +194,7 @@ __global__ void __launch_bounds__(K * kWave, 4)
   {
     V4* z = reinterpret_cast<V4*>(lds);
     const V4 zero = {};
-    for (int i = threadIdx.x; i < lw_lds_bytes(K, NB) / 16; i += K * kWave) z[i] = zero;
+    for (int i = threadIdx.x; i < lw_lds_bytes(K, NB, R) / 16; i += K * kWave) z[i] = zero;
   }
   asm volatile("s_waitcnt vmcnt(0)" : "+v"(YP[1][0][0]), "+v"(YP[1][0][1])::"memory");
   __syncthreads();
@@ -224,12 +233,13 @@ __global__ void __launch_bounds__(K * kWave, 4)
       // the batch of column p + R - 1 goes into the slot of column p - 1, read (and waited for) in the previous step
       if (lw_loaded(K, xa, xb, nx, p + R - 1)) ring_issue(p + R - 1);
       if (lw_loaded(K, xa, xb, nx, p)) {
-        // batches issued behind column p's: those of p + 1 .. p + R - 1 that exist (the loaded columns are one range)
-        static_assert(R == 3, "the counted waits below are written for three slots");
-        if (lw_loaded(K, xa, xb, nx, p + 2)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NB) : "memory");
+        // batches issued behind column p's (lw_ring_wait): those of p + 1 .. p + R - 1 that exist (the loaded columns are one range)
+        //   R = 3:  p + 2 loaded: 2 batches   else p + 1 loaded: 1 batch   else none
+        //   R = 2:                            p + 1 loaded: 1 batch        else none
+        if (R == 3 && lw_loaded(K, xa, xb, nx, p + 2)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NB) : "memory");
         else if (lw_loaded(K, xa, xb, nx, p + 1)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NB) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        column_read((unsigned)lw_ring_slot(p) * kSlot);
+        column_read((unsigned)lw_ring_slot(p, R) * kSlot);
       }
     } else if (t >= 1) {
       column_read(link_in + (unsigned)(1 - nw) * kSlot);
@@ -253,14 +263,18 @@ __global__ void __launch_bounds__(K * kWave, 4)
   }
 }
 
+// ring: the depth of the input ring, lw_ring_depth(K, b_per_pixel) or kLevelWaveRing (the instances built)
 template <int K>
-int launch_iterk_levelwave(int g_fn, bool b_per_pixel, dim3 grid, hipStream_t s, float* x_out, float* y_out, const float* x, const float* y,
+int launch_iterk_levelwave(int g_fn, bool b_per_pixel, int ring, dim3 grid, hipStream_t s, float* x_out, float* y_out, const float* x, const float* y,
                            const FusedArgs<float>& a, const StepsK<K>& sp, const PdhgRecord<float>* rec, unsigned* place) {
   const dim3 blockw(K * kWave);
-#define GOW(G, BP) PH_LAUNCH((fused_iter2d_xkw_kernel<K, G, BP>), grid, blockw, 0, s, x_out, y_out, x, y, a, sp, rec, nullptr)
+  if (ring != kLevelWaveRing && ring != lw_ring_depth(K, b_per_pixel)) { set_error("fused K-iteration launch (level per wavefront): no instance with that ring depth"); return 1; }
+#define GOWR(G, BP, RD) PH_LAUNCH((fused_iter2d_xkw_kernel<K, G, BP, RD>), grid, blockw, 0, s, x_out, y_out, x, y, a, sp, rec, nullptr)
+#define GOW(G, BP) do { if (ring == kLevelWaveRing) GOWR(G, BP, kLevelWaveRing); else GOWR(G, BP, lw_ring_depth(K, BP)); } while (0)
   if constexpr (K == 4) {
-    if (place) {
-      PH_LAUNCH((fused_iter2d_xkw_kernel<4, PROST_FN_SQUARE, true, true>), grid, blockw, 0, s, x_out, y_out, x, y, a, sp, rec, place);
+    if (place) {          // the instance that ships: the ring depth of the headline launch
+      if (ring != lw_ring_depth(4, true)) { set_error("fused K-iteration launch: the placement record exists for the default ring depth"); return 1; }
+      PH_LAUNCH((fused_iter2d_xkw_kernel<4, PROST_FN_SQUARE, true, lw_ring_depth(4, true), true>), grid, blockw, 0, s, x_out, y_out, x, y, a, sp, rec, place);
       hipError_t e_ = hipGetLastError();
       return e_ != hipSuccess ? fail(e_, "fused K-iteration kernel (level per wavefront, placement record)") : 0;
     }
@@ -268,12 +282,13 @@ int launch_iterk_levelwave(int g_fn, bool b_per_pixel, dim3 grid, hipStream_t s,
   if (g_fn == PROST_FN_SQUARE) { if (b_per_pixel) GOW(PROST_FN_SQUARE, true); else GOW(PROST_FN_SQUARE, false); }
   else { if (b_per_pixel) GOW(PROST_FN_ABS, true); else GOW(PROST_FN_ABS, false); }
 #undef GOW
+#undef GOWR
   { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return fail(e_, "fused K-iteration kernel (level per wavefront)"); }
   return 0;
 }
-template int launch_iterk_levelwave<3>(int, bool, dim3, hipStream_t, float*, float*, const float*, const float*, const FusedArgs<float>&, const StepsK<3>&,
+template int launch_iterk_levelwave<3>(int, bool, int, dim3, hipStream_t, float*, float*, const float*, const float*, const FusedArgs<float>&, const StepsK<3>&,
                                        const PdhgRecord<float>*, unsigned*);
-template int launch_iterk_levelwave<4>(int, bool, dim3, hipStream_t, float*, float*, const float*, const float*, const FusedArgs<float>&, const StepsK<4>&,
+template int launch_iterk_levelwave<4>(int, bool, int, dim3, hipStream_t, float*, float*, const float*, const float*, const FusedArgs<float>&, const StepsK<4>&,
                                        const PdhgRecord<float>*, unsigned*);
 
 }  // namespace prost_hip

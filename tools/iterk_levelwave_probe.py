@@ -1,9 +1,12 @@
 """Exact-class K-iteration launches through the kernel C ABI: time of one launch per (K, cols), against the plain pair launch.
 usage: iterk_levelwave_probe.py [N] [K,K,...] [cols,cols,...]      (PROST_ITERK_LEVELWAVE=0: the single-wave instances)
+       iterk_levelwave_probe.py ring [N] [cols,cols,...]           K = 4: the two-slot ring against the three-slot one, length by length
        iterk_levelwave_probe.py place [N]
 Prints one line per (K, cols): ms per launch, us per iteration, and the two pair launches a launch of four replaces.
 place: where the wavefronts of the K = 4 launch (square, per-pixel b, auto chunk length) ran -- every wave records its HW_ID and XCC_ID
-after its last step: workgroups per CU, which workgroups share a CU, wave -> SIMD, distinct levels per SIMD, launch against launch."""
+after its last step: workgroups per CU, which workgroups share a CU, wave -> SIMD, distinct levels per SIMD, launch against launch.
+ring: PROST_ITERK_LW_RING is read per launch, so both depths run in one process, alternating, on the same buffers (cols 0: each
+depth's own rule)."""
 import ctypes as C
 import os
 import sys
@@ -70,6 +73,46 @@ def main(N=4096, ks=(3, 4), cols_list=(0,), iters=200):
                 N, k, cols, L_.prost_hip_fused_iterationk_chunk_cols(C.byref(d), 0, k, 0), t, 1e3 * t / k, 100 * (t / k - pair / 2) / (pair / 2)), flush=True)
 
 
+def ring(N=4096, cols_list=(0,), iters=200, rounds=3):
+    """K = 4, square, per-pixel b: ms per launch with two and with three ring slots at every chunk length, `rounds` times alternating"""
+    hip.require_device()
+    d, f, x, y = _setup(N)
+    L_ = hip.lib()
+    IK = L_.prost_hip_fused_iterationk_f32
+    taus = (C.c_double * 4)(0.3, 0.29, 0.28, 0.27); sigmas = (C.c_double * 4)(1.0, 1.03, 1.06, 1.09); thetas = (C.c_double * 4)(0.9, 0.91, 0.92, 0.93)
+    ev = [C.c_void_p() for _ in range(2)]
+    for e in ev:
+        hip.check(L_.prost_hip_event_create(C.byref(e)))
+
+    def timed(cols):
+        for i in range(10):
+            hip.check(IK(C.byref(d), 4, x[(i + 1) % 2].ptr, y[(i + 1) % 2].ptr, x[i % 2].ptr, y[i % 2].ptr, taus, sigmas, thetas, cols, None, None, None))
+        hip.sync()
+        hip.check(L_.prost_hip_event_record(ev[0], None))
+        for i in range(iters):
+            hip.check(IK(C.byref(d), 4, x[(i + 1) % 2].ptr, y[(i + 1) % 2].ptr, x[i % 2].ptr, y[i % 2].ptr, taus, sigmas, thetas, cols, None, None, None))
+        hip.check(L_.prost_hip_event_record(ev[1], None))
+        hip.check(L_.prost_hip_event_synchronize(ev[1]))
+        ms = C.c_float(); hip.check(L_.prost_hip_event_elapsed_ms(ev[0], ev[1], C.byref(ms)))
+        return ms.value / iters
+
+    for cols in cols_list:
+        got = {"2": [], "3": []}
+        auto = {}
+        for _ in range(rounds):
+            for depth in ("3", "2"):
+                if depth == "3":
+                    os.environ["PROST_ITERK_LW_RING"] = "3"
+                else:
+                    os.environ.pop("PROST_ITERK_LW_RING", None)
+                auto[depth] = L_.prost_hip_fused_iterationk_chunk_cols(C.byref(d), 0, 4, 0)
+                got[depth].append(timed(cols))
+        os.environ.pop("PROST_ITERK_LW_RING", None)
+        m2, m3 = sorted(got["2"])[rounds // 2], sorted(got["3"])[rounds // 2]
+        print("N=%d K=4 cols=%-3d (auto: 3 slots %d, 2 slots %d): 3 slots %s ms, 2 slots %s ms, medians %.4f -> %.4f (%+.1f %%)" % (
+            N, cols, auto["3"], auto["2"], " ".join("%.4f" % v for v in got["3"]), " ".join("%.4f" % v for v in got["2"]), m3, m2, 100 * (m2 - m3) / m3), flush=True)
+
+
 def _hist(values):
     h = {}
     for v in values:
@@ -110,16 +153,17 @@ def place(N=4096, K=4):
         for b in range(grid):
             on.setdefault(int(cu[b, 0]), []).append(b)
         print("  CUs used: %d; workgroups per CU: %s" % (len(on), _hist(len(v) for v in on.values())))
-        print("  differences of the workgroups that share a CU (to the lowest b): %s" % _hist(tuple(b - v[0] for b in v[1:]) for v in on.values() if len(v) == 4))
+        most = max(len(v) for v in on.values())
+        print("  differences of the workgroups that share a CU (to the lowest b): %s" % _hist(tuple(b - v[0] for b in v[1:]) for v in on.values() if len(v) == most))
         for c in sorted(on)[:4]:
             print("    CU %03x: b = %s" % (c, on[c]))
         levels = []
         for c, v in on.items():
-            if len(v) == 4:
+            if len(v) == most:
                 for sd in range(4):
                     levels.append(len({k + 1 for b in v for k in range(K) if simd[b, k] == sd}))          # wave k carries level k + 1
         share = sum(1 for v in levels if v >= 3) / max(1, len(levels))
-        print("  CUs with four workgroups: distinct levels per SIMD: %s; SIMDs with >= 3 levels: %.1f %%" % (_hist(levels), 100 * share))
+        print("  CUs with %d workgroups: distinct levels per SIMD: %s; SIMDs with >= 3 levels: %.1f %%" % (most, _hist(levels), 100 * share))
         if w is not first:
             print("  against the first launch: same CU for %d of %d workgroups, same SIMD for %d of %d waves" % (
                 int((((first >> 8) & 0xfff)[:, 0] == cu[:, 0]).sum()), grid, int((((first >> 4) & 3) == simd).sum()), grid * K), flush=True)
@@ -128,6 +172,9 @@ def place(N=4096, K=4):
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "place":
         place(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "ring":
+        ring(int(sys.argv[2]) if len(sys.argv) > 2 else 4096, tuple(int(v) for v in sys.argv[3].split(",")) if len(sys.argv) > 3 else (0,))
         sys.exit(0)
     N = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
     ks = tuple(int(v) for v in sys.argv[2].split(",")) if len(sys.argv) > 2 else (3, 4)
