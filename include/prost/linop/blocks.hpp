@@ -7,6 +7,7 @@
 #include "prost/linop/conv2d.hpp"
 #include "prost/linop/conv2d_strided.hpp"
 #include "prost/linop/fft2d.hpp"
+#include "prost/linop/hessian2d.hpp"
 #include "prost/linop/radon2d.hpp"
 #include "prost/linop/sample2d.hpp"
 #include "prost/linop/sym_gradient2d.hpp"
@@ -483,6 +484,35 @@ class BlockNonlocalGradient2D : public ProductBlock<T> {
   std::vector<signed char> pairs_;  ///< (dy, dx) pairs as the entry points take them
   std::vector<T> weights_;          ///< rounded once to T
   device_vector<T> d_weights_;
+};
+
+/// the second-order differences H = E grad (u_xx, u_yy, u_xy) of L channels of an ny x nx grid, without a matrix and without the
+/// intermediate field: the operator of TV^2 and of the Hessian-Schatten norms.  components = 3: 3 L N rows (hxx, hyy, hxy planes, the
+/// range layout of sym_gradient2d); components = 4: 4 L N rows (hxx, hxy, hxy, hyy, the column-major symmetric 2 x 2 matrix); L N
+/// columns.  The bits are those of gradient2d and sym_gradient2d chained.  Arithmetic, sums and error bound: prost/linop/hessian2d.hpp.
+/// No describe(): the block runs on the generic paths.  Nothing is stored on the device.
+template <typename T>
+class BlockHessian2D : public ProductBlock<T> {
+ public:
+  /// checks every argument (messages start with "BlockHessian2D: "); declared_rows / declared_cols < 0: no size was declared
+  static BlockHessian2D<T>* Create(size_t row, size_t col, double nx, double ny, double L, double w, double components, double declared_rows = -1,
+                                   double declared_cols = -1);
+  virtual void Initialize() {}
+  virtual void Release() {}
+  virtual T row_sum(size_t row, T alpha) const;
+  virtual T col_sum(size_t col, T alpha) const;
+  virtual void row_sums(T* out, T alpha) const;              ///< closed forms, one pass over the pixels
+  virtual void col_sums(T* out, T alpha) const;
+  virtual size_t gpu_mem_amount() const { return 0; }
+
+ protected:
+  BlockHessian2D(size_t row, size_t col, size_t nx, size_t ny, size_t L, double w, int components)
+      : ProductBlock<T>(row, col, (size_t)components * L * nx * ny, L * nx * ny), nx_(nx), ny_(ny), L_(L), w_(w), components_(components) {}
+  virtual void Product(T* res, const T* rhs, bool transpose, bool accumulate);
+  double WeightPower(T alpha) const { return hessian2d::WeightPower((double)hessian2d::RoundWeight<T>(w_), (double)alpha); }
+  size_t nx_, ny_, L_;
+  double w_;               ///< as given; the kernels and the sums round it to T once
+  int components_;
 };
 
 /// constant-coefficient multi-diagonal block; `identity` maps here (block_diags.hpp, identity.m:11-12)

@@ -419,6 +419,29 @@ int prost_hip_linop_tensor_gradient2d_f64(double* res, const double* rhs, const 
  * Duplicate offsets are not looked for, and the values of the weights are the caller's: BlockNonlocalGradient2D refuses both. */
 int prost_hip_linop_nonlocal_gradient2d_f32(float* res, const float* rhs, const float* weights, size_t nx, size_t ny, size_t L, int M, const signed char* offsets, int transpose, int accumulate, void* stream);
 int prost_hip_linop_nonlocal_gradient2d_f64(double* res, const double* rhs, const double* weights, size_t nx, size_t ny, size_t L, int M, const signed char* offsets, int transpose, int accumulate, void* stream);
+/* BlockHessian2D (additions; ABI version unchanged; kernels_linop_hessian2d.hip, arithmetic and order of operations:
+ * prost/linop/hessian2d.hpp): the second-order differences H = E grad of L channels of an ny x nx grid without the intermediate field,
+ * grad = gradient2d(nx, ny, L), E = sym_gradient2d(nx, ny, L, w); N = nx ny, pixel (y, x) at p = y + x ny.  Domain, L N values: u_c[p]
+ * at c N + p.  Range, components == 3: 3 L N values, hxx_c[p] at c N + p, hyy_c[p] at (L + c) N + p, hxy_c[p] at (2 L + c) N + p;
+ * components == 4: 4 L N values, the planes (hxx, hxy, hxy, hyy) at (k L + c) N + p.  With ax = [x < nx-1], bx = [x > 0],
+ * ay = [y < ny-1], by = [y > 0]; every difference, product and addition is rounded once, w is rounded to T once, an outer sum starts
+ * from +0 and adds its present terms left to right, a masked term is absent (selected away), a masked inner difference is +0:
+ *   inner            gx[p] = (ax) u[p+ny] - u[p], else +0;   gy[p] = (ay) u[p+1] - u[p], else +0
+ *   transpose == 0:  hxx[p] = (bx) -gx[p-ny], (ax) +gx[p];   hyy[p] = (by) -gy[p-1], (ay) +gy[p];
+ *                    hxy[p] = (by) -(w gx[p-1]), (ay) +(w gx[p]), (bx) -(w gy[p-ny]), (ax) +(w gy[p])        (components == 4: stored twice)
+ *   transpose != 0:  (components == 4: exy = e_xy + e_yx, planes 1 and 2, one rounding)
+ *                    vx[p] = (ax) +exx[p], (ax) -exx[p+ny], (ay) +(w exy[p]), (ay) -(w exy[p+1]);
+ *                    vy[p] = (ay) +eyy[p], (ay) -eyy[p+1], (ax) +(w exy[p]), (ax) -(w exy[p+ny]);
+ *                    divx = (ax) vx[p], else +0, (bx) divx -= vx[p-ny];   divy = (ay) vy[p], else +0, (by) divy -= vy[p-1];
+ *                    res = 0 - (divx + divy)        (accumulate: res - (divx + divy))
+ * accumulate != 0 stores res + value in the forward product.  The bits are those of prost_hip_grad2d_fwd followed by
+ * prost_hip_linop_sym_gradient2d, and of the latter's adjoint followed by prost_hip_grad2d_adj, signed zeros included.  Any alignment
+ * of T is accepted (16-byte aligned pointers and a height that is a multiple of 16 / sizeof(T) take the vector kernels; the bits are
+ * the same).  Aliasing: res and rhs must NOT overlap.  No atomics: a call repeats its bits.  No allocation, copy or synchronisation.
+ * Refused without a launch: nx, ny or L of 0, w not finite, w zero after rounding to T, components other than 3 or 4, null pointers,
+ * components L N beyond 2^53. */
+int prost_hip_hessian2d_f32(float* res, const float* rhs, size_t nx, size_t ny, size_t L, double w, int components, int transpose, int accumulate, void* stream);
+int prost_hip_hessian2d_f64(double* res, const double* rhs, size_t nx, size_t ny, size_t L, double w, int components, int transpose, int accumulate, void* stream);
 /* x = beta * x (beta == 0 -> zero fill): thrust::fill / transform at linearoperator.cu:140-147 */
 /* x[i] = value (thrust::fill, linearoperator.cu:140-147; also used for preconditioners that are one constant: the
  * gradient blocks' row / column sums are, block_gradient2d.cu:154-163, so nothing is uploaded for them) */

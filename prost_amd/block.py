@@ -456,6 +456,36 @@ def sym_gradient2d(nx, ny, L=1, w=math.sqrt(0.5)):
     return lambda row, col, nrows, ncols: [["sym_gradient2d", row, col, data], sz]
 
 
+HESSIAN2D_MAX_SIZE = 2 ** 53               # sizes travel as doubles
+
+
+def hessian2d(nx, ny, L=1, w=math.sqrt(0.5), components=3):
+    """The second-order differences H = E grad of L channels of an ny x nx grid, applied without a matrix and without the intermediate
+    field: the operator of second-order total variation (TV^2, bounded Hessian), of the TV + TV^2 infimal convolution and of the
+    Hessian-Schatten-norm regularisers.  grad is gradient2d(nx, ny, L), E is sym_gradient2d(nx, ny, L, w), and the products have the
+    bits of the two blocks chained.  N = nx ny, pixel (y, x) at p = y + x ny.  Domain, L N values: u_c[p] at c N + p.
+    components = 3: range of 3 L N values in the layout of sym_gradient2d, hxx_c[p] at c N + p, hyy_c[p] at (L + c) N + p, hxy_c[p] at
+    (2 L + c) N + p, so sum_norm2(3, False, ..) groups per channel and pixel; with w = sqrt(1/2) its 2-norm is the Frobenius norm of the
+    Hessian.  components = 4: range of 4 L N values, the planes (hxx, hxy, hxy, hyy) at (k L + c) N + p, the column-major symmetric
+    2 x 2 matrix sum_eigen_2x2(False, ..) reads; w = 0.5 gives the true Hessian.  The default of w is sqrt(1/2) whatever components
+    is.  Interior rows: hxx and hyy are (1, -2, 1), hxy is the 7-point stencil with centre -2 w; the edges lose the masked terms, and
+    nx = 1 or ny = 1 are legal (hxx or hyy and hxy are then zero).  w has to be non-zero, as in sym_gradient2d."""
+    nx, ny, L = [_integer("hessian2d", name, v) for name, v in (("nx", nx), ("ny", ny), ("L", L))]
+    if isinstance(w, bool) or not isinstance(w, _NUMBER) or not np.isfinite(w):
+        raise ValueError("hessian2d: w = %r is not a finite number" % (w,))
+    w = float(w)
+    if w == 0:
+        raise ValueError("hessian2d: w has to be non-zero")
+    if isinstance(components, bool) or not isinstance(components, _NUMBER) or components not in (3, 4):
+        raise ValueError("hessian2d: components = %r has to be 3 or 4" % (components,))
+    components = int(components)
+    if components * L * nx * ny > HESSIAN2D_MAX_SIZE:
+        raise ValueError("hessian2d: components L nx ny = %d rows; the size has to stay within 2^53" % (components * L * nx * ny))
+    sz = [components * L * nx * ny, L * nx * ny]
+    data = [nx, ny, L, w, components]
+    return lambda row, col, nrows, ncols: [["hessian2d", row, col, data], sz]
+
+
 TENSOR_GRADIENT2D_MAX_SIZE = 2 ** 53       # sizes travel as doubles
 
 

@@ -512,6 +512,12 @@ std::map<std::string, typename Factory<T>::BlockFactory>& Factory<T>::block_reg(
       const std::vector<double> weights = full_vector(d, 4, "BlockNonlocalGradient2D: the weights have to be a full vector of type single or double.");
       return BlockNonlocalGradient2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), offsets, weights, size.first, size.second);
     };
+    // the second-order differences of TV^2: cells { nx, ny, L, w, components }
+    reg["hessian2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
+      const auto size = declared_size(d, 5, "BlockHessian2D: the data cells are { nx, ny, L, w, components } or { nx, ny, L, w, components, nrows, ncols }.");
+      return BlockHessian2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), GetScalarFromCell(d, 3),
+                                       GetScalarFromCell(d, 4), size.first, size.second);
+    };
     // the dense blocks (factory.cpp:590-601, :694-716): cell 0 is a full matrix, column-major, converted to T.  A sparse cell is refused:
     // the reference would read its value array as if it were the full matrix.
     auto dense_data = [](const prost_value* pm) {

@@ -40,6 +40,7 @@ template <typename T> struct Api;
     static constexpr auto linop_sym_gradient2d = prost_hip_linop_sym_gradient2d_##S; \
     static constexpr auto linop_tensor_gradient2d = prost_hip_linop_tensor_gradient2d_##S; \
     static constexpr auto linop_nonlocal_gradient2d = prost_hip_linop_nonlocal_gradient2d_##S; \
+    static constexpr auto hessian2d = prost_hip_hessian2d_##S; \
     static constexpr auto prox_elem = prost_hip_prox_elem_##S;                    \
     static constexpr auto prox_elem_moreau = prost_hip_prox_elem_moreau_##S;      \
     static constexpr auto prox_elem_arg = prost_hip_prox_elem_arg_##S;            \

@@ -1079,6 +1079,47 @@ void BlockNonlocalGradient2D<T>::Product(T* r, const T* x, bool transpose, bool 
 template class BlockNonlocalGradient2D<float>;
 template class BlockNonlocalGradient2D<double>;
 
+// ---- the second-order differences H = E grad of TV^2, without a matrix ----
+template <typename T>
+BlockHessian2D<T>* BlockHessian2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, double w, double components, double declared_rows,
+                                             double declared_cols) {
+  const char* kName = "BlockHessian2D";
+  CheckIntegers(kName, {{"nx", nx}, {"ny", ny}, {"L", L}}, kTwo53, " has to be a positive integer.");
+  if (!std::isfinite(w)) Refuse(kName, "w = ", w, " has to be finite.");
+  if (w == 0) Refuse(kName, "w has to be non-zero.");
+  const T wt = hessian2d::RoundWeight<T>(w);
+  if (wt == (T)0 || !std::isfinite((double)wt)) Refuse(kName, "w = ", w, " is zero or not finite", PrecisionStop<T>());
+  if (!(components == 3 || components == 4)) Refuse(kName, "components = ", components, " has to be 3 (hxx, hyy, hxy) or 4 (hxx, hxy, hxy, hyy).");
+  const double rows = components * L * nx * ny, cols = L * nx * ny;
+  if (!(components * L * (nx * ny) <= kTwo53) || !(nx * ny <= kTwo53)) Refuse(kName, "components L nx ny = ", rows, " rows; the size has to stay within 2^53.");
+  CheckDeclaredSize(kName, declared_rows, declared_cols, rows, cols, "components L nx ny x L nx ny");
+  return new BlockHessian2D<T>(row, col, (size_t)nx, (size_t)ny, (size_t)L, w, (int)components);
+}
+template <typename T>
+T BlockHessian2D<T>::row_sum(size_t row, T alpha) const {
+  return (T)hessian2d::RowSum(row, nx_, ny_, L_, components_, WeightPower(alpha), hessian2d::TwoPower((double)alpha));
+}
+template <typename T>
+T BlockHessian2D<T>::col_sum(size_t col, T alpha) const {
+  return (T)hessian2d::ColSum(col, nx_, ny_, components_, WeightPower(alpha), hessian2d::TwoPower((double)alpha));
+}
+template <typename T>
+void BlockHessian2D<T>::row_sums(T* out, T alpha) const {
+  const size_t N = nx_ * ny_;
+  for (size_t k = 0; k < (size_t)components_; k++)             // the L planes of component k are the same
+    AddPlaneSums(out + k * L_ * N, N, L_, [&](size_t p) { return row_sum(k * L_ * N + p, alpha); });
+}
+template <typename T>
+void BlockHessian2D<T>::col_sums(T* out, T alpha) const {
+  AddPlaneSums(out, nx_ * ny_, L_, [&](size_t p) { return col_sum(p, alpha); });
+}
+template <typename T>
+void BlockHessian2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
+  CheckHip(Api<T>::hessian2d(r, x, nx_, ny_, L_, w_, components_, transpose ? 1 : 0, acc ? 1 : 0, CurrentStream()), "hessian2d");
+}
+template class BlockHessian2D<float>;
+template class BlockHessian2D<double>;
+
 // ---- diags block ----
 static bool g_diags_quirk = false;
 template <typename T> void BlockDiags<T>::SetReferenceGridQuirk(bool on) { g_diags_quirk = on; }
