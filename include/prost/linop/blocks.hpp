@@ -2,6 +2,8 @@
 // (reference: include/prost/linop/block_{gradient2d,gradient3d,sparse,dense,dense_kron_id,id_kron_dense,diags,zero}.hpp).
 #ifndef PROST_LINOP_BLOCKS_HPP_
 #define PROST_LINOP_BLOCKS_HPP_
+#include <mutex>
+
 #include "prost/device_vector.hpp"
 #include "prost/linop/block.hpp"
 #include "prost/linop/conv2d.hpp"
@@ -10,6 +12,7 @@
 #include "prost/linop/hessian2d.hpp"
 #include "prost/linop/radon2d.hpp"
 #include "prost/linop/sample2d.hpp"
+#include "prost/linop/sense2d.hpp"
 #include "prost/linop/sym_gradient2d.hpp"
 #include "prost/linop/tensor_gradient2d.hpp"
 #include "prost/linop/nonlocal_gradient2d.hpp"
@@ -365,6 +368,43 @@ class BlockFFT2D : public ProductBlock<T> {
   std::vector<T> table_;                   ///< fft2d::MakeTable
   double sums1_[fft2d::kMaxLog2 + 1];      ///< fft2d::SumTable at alpha = 1, made at creation: what row-by-row callers of row_sum ask for
   device_vector<T> d_table_, d_work_;
+};
+
+/// the multi-coil Fourier operator of SENSE-type parallel MRI, K u = [ F (sigma_c . u) ]_c, and its transpose, without a matrix: L complex
+/// images of ny x nx (the domain of BlockFFT2D with L images) onto L C k-space images (the range of BlockFFT2D with L C images, image
+/// l C + c is coil c of image l), with C = 1 .. 64 complex sensitivity maps shared by the images.  2 L C N rows by 2 L N columns, N = nx ny.
+/// Arithmetic, order of the coil sum, error bound and why the sums are bounds, not the matrix's sums: prost/linop/sense2d.hpp.  No
+/// describe(): the block runs on the generic paths.  Stored on the device: the maps (2 C N values), BlockFFT2D's table and one work buffer
+/// of 2 L C N values between the two passes.
+template <typename T>
+class BlockSense2D : public ProductBlock<T> {
+ public:
+  /// checks every argument (messages start with "BlockSense2D: "); maps: 2 C nx ny values, the C real planes first, then the C imaginary
+  /// planes; declared_rows / declared_cols < 0: no size was declared
+  static BlockSense2D<T>* Create(size_t row, size_t col, double nx, double ny, double L, double C, const std::vector<double>& maps, double declared_rows = -1,
+                                 double declared_cols = -1);
+  virtual void Initialize();
+  virtual void Release();
+  virtual T row_sum(size_t row, T alpha) const;              ///< the bound Rbar_c of sense2d.hpp: a look-up while alpha stays the one asked last, else O(C N) once
+  virtual T col_sum(size_t col, T alpha) const;              ///< the bound Cbar(p): O(C) per call
+  virtual void row_sums(T* out, T alpha) const;              ///< C bounds, each added to the 2 L planes of its coil
+  virtual void col_sums(T* out, T alpha) const;              ///< one pass over the pixels
+  virtual size_t gpu_mem_amount() const { return (table_.size() + maps_.size() + this->nrows()) * sizeof(T); }
+  const sense2d::Geometry& geometry() const { return geometry_; }
+
+ protected:
+  BlockSense2D(size_t row, size_t col, size_t nrows, size_t ncols) : ProductBlock<T>(row, col, nrows, ncols) {}
+  virtual void Product(T* res, const T* rhs, bool transpose, bool accumulate);
+  sense2d::Geometry geometry_;
+  std::vector<T> table_;                   ///< fft2d::MakeTable
+  std::vector<T> maps_;                    ///< rounded once to T
+  /// sense2d::RowBound of coil c: the C bounds of the alpha asked last are kept (alpha = 1 from creation), since row-by-row callers of
+  /// row_sum ask every row for the same alpha and one bound costs a pass over a map
+  double RowBoundOf(double alpha, size_t c) const;
+  mutable std::mutex rows_lock_;
+  mutable double rows_alpha_ = 1;
+  mutable std::vector<double> rows_;
+  device_vector<T> d_table_, d_maps_, d_work_;
 };
 
 /// the orthogonal, periodised, separable multi-level wavelet transform of L planes of ny x nx and its transpose, the inverse transform,

@@ -336,6 +336,35 @@ typedef struct prost_hip_fft2d_geometry {
 } prost_hip_fft2d_geometry;
 int prost_hip_fft2d_f32(const prost_hip_fft2d_geometry* geometry, const float* table, float* work, float* res, const float* rhs, int accumulate, void* stream);
 int prost_hip_fft2d_f64(const prost_hip_fft2d_geometry* geometry, const double* table, double* work, double* res, const double* rhs, int accumulate, void* stream);
+/* BlockSense2D (additions; ABI version unchanged; kernels_linop_sense2d.hip, arithmetic and order of operations: prost/linop/sense2d.hpp):
+ * the multi-coil Fourier operator of SENSE-type parallel MRI, K u = [ F (sigma_c . u) ]_c, and its transpose K^T y = sum_c conj(sigma_c) .
+ * F^H y_c, for `planes` complex images of ny x nx that share `coils` complex sensitivity maps; F is the transform of prost_hip_fft2d.
+ * N = nx ny, pixel (y, x) at p = y + x ny.  Domain, 2 planes N values: re_l at l N, im_l at (planes + l) N.  Range, 2 planes coils N values:
+ * image j = l coils + c holds coil c of image l, re_j at j N, im_j at (planes coils + j) N.  maps: 2 coils N values of T in device memory,
+ * real planes first (re sigma_c at c N, im sigma_c at (coils + c) N).
+ *   transpose == 0:  z = sigma_c u_l per pixel (z.re = u.re s.re - u.im s.im, z.im = u.re s.im + u.im s.re), then prost_hip_fft2d's forward
+ *                    product on the planes coils images z: the bits of that call on the premultiplied planes
+ *   transpose != 0:  v = prost_hip_fft2d's transposed product of every range image, scaling included; the term of coil c is
+ *                    (v.re s.re + v.im s.im, v.im s.re - v.re s.im); the terms are summed in ascending c starting from the term of coil 0
+ * every product and sum rounded once.  The geometry record is a HOST pointer, read before the call returns.  table: as for
+ * prost_hip_fft2d.  work: 2 planes coils N values of T in device memory, overwritten when nx > 1 and ny > 1, untouched otherwise.
+ * accumulate != 0 stores res + value instead of value.  Any element offset of res, rhs, work and maps is accepted.  Aliasing: res, rhs,
+ * work, maps and table must NOT overlap.  A non-finite value of image l reaches the coil images of l only, one of coil image (l, c) image
+ * l of the transpose only; none causes a fault.  No atomics: a call repeats its bits.  Side effects: no allocation, copy or
+ * synchronisation.  Refused without a launch: a null pointer, nx or ny that is no power of two from 1 to 2048, planes below 1, coils
+ * outside 1 .. 64, 2 planes coils N of 2^31 or more. */
+typedef struct prost_hip_sense2d_geometry {
+  int32_t ny, nx;       /* image plane */
+  int32_t planes;       /* complex images L */
+  int32_t coils;        /* sensitivity maps C */
+  int32_t transpose;
+  int32_t slab;         /* tile of the coil-summing pass of the transposed product: 0 the library's choice, 1 the small tile (2048 / nx rows
+                           side by side), 2 the choice of prost_hip_fft2d; the result does not depend on it, only the time; else refused */
+} prost_hip_sense2d_geometry;
+int prost_hip_sense2d_f32(const prost_hip_sense2d_geometry* geometry, const float* table, const float* maps, float* work, float* res, const float* rhs, int accumulate,
+                          void* stream);
+int prost_hip_sense2d_f64(const prost_hip_sense2d_geometry* geometry, const double* table, const double* maps, double* work, double* res, const double* rhs, int accumulate,
+                          void* stream);
 /* BlockWavelet2D (additions; ABI version unchanged; kernels_linop_wavelet2d.hip, arithmetic, order of operations, limits and the slots of
  * the work buffer: prost/linop/wavelet2d.hpp): the orthogonal, periodised, separable multi-level discrete wavelet transform K (Mallat's
  * pyramid) of `planes` real planes of ny x nx and its transpose, the inverse transform.  N = nx ny, pixel (y, x) of plane c at

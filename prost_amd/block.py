@@ -365,6 +365,96 @@ def fft2d(nx, ny, L=1):
     return lambda row, col, nrows, ncols: [["fft2d", row, col, data], sz]
 
 
+SENSE2D_MAX_COILS = 64
+
+
+def sense2d(nx, ny, maps, L=1):
+    """The multi-coil Fourier operator of SENSE-type parallel MRI, K u = [ F (sigma_1 . u) ; .. ; F (sigma_C . u) ], applied without a
+    matrix as a real 2 L C N x 2 L N operator, N = nx ny: F is fft2d, "." the pointwise complex product, sigma_c the complex sensitivity
+    map of coil c; K^T y = sum_c conj(sigma_c) . F^H y_c.  The coil product happens while the first pass loads, the coil sum in registers
+    while the last pass of the transpose stores: there is no field of C intermediate images and no atomic.  Domain: the domain of
+    fft2d(nx, ny, L), re_l[p] at l N + p and im_l[p] at (L + l) N + p with p = y + x ny (L frames of a dynamic series or several contrasts
+    share the maps).  Range: the range of fft2d(nx, ny, L C), image j = l C + c holds coil c of image l, so a sampling mask is coefficient
+    c of sum_1d("square", 1, d, mask, 0, 0) on all C k-space images, as in examples/sense_mri.py.  nx and ny are powers of two from 1 to
+    2048, C = 1 .. 64, 2 L C nx ny < 2^31.
+    maps: a complex (C, ny, nx) array m[c, y, x], a complex (C, N) array (each plane flattened with y fastest), a sequence of C complex
+    planes, each an (ny, nx) array or a vector of N values, or a pair (re, im) of real arrays of those shapes.  Every value is rounded once
+    to the precision of the problem and the operator is defined with the rounded maps; zeros are legal (a map may vanish everywhere),
+    non-finite values are refused.  With C = 1 and sigma = 1 the block is fft2d up to the signs of zeros.  The device holds the maps
+    (2 C N values), fft2d's table and one work buffer of 2 L C N values.
+    Preconditioning: the phase of the maps shifts every angle of the Fourier matrix, so the sums of |K|^e have no closed form except at
+    e = 2 and the block returns upper BOUNDS, row (l, c, q): f(e) s^e sum_p |sigma_c(p)|^e, column of pixel p: f(e) s^e N sum_c
+    |sigma_c(p)|^e, s = 1 / sqrt(N), f(e) = max(1, 2^(1 - e/2)); S <= Sbar <= 2^|1 - e/2| S, exact at e = 2.  Bounds from above only
+    shrink the diagonal steps; convergence (Pock & Chambolle 2011, Lemma 2) holds unchanged.  As for fft2d a diagonal preconditioner of
+    this dense operator is very conservative: use prob.set_scaling_identity(), as the example does (with sum_c |sigma_c|^2 = 1 the
+    operator's norm is 1)."""
+    for name, v in (("nx", nx), ("ny", ny)):
+        n = _integer("sense2d", name, v)
+        if n > FFT2D_MAX_SIDE or n & (n - 1):
+            raise ValueError("sense2d: %s = %r has to be a power of two from 1 to %d" % (name, v, FFT2D_MAX_SIDE))
+    nx, ny, L = int(nx), int(ny), _integer("sense2d", "L", L)
+    N = nx * ny
+
+    def array(v, kinds, what):
+        try:
+            a = np.asarray(v)
+            if a.dtype.kind not in kinds:
+                raise TypeError
+            return a
+        except (TypeError, ValueError):
+            raise ValueError("sense2d: %s" % what)
+
+    def planes(a, what):
+        """a (C, ny, nx), (C, N), (ny, nx) or (N,) array -> (C, N), p = y + x ny"""
+        if a.ndim == 3 and a.shape[1:] == (ny, nx):
+            return a.transpose(0, 2, 1).reshape(a.shape[0], N)
+        if a.ndim == 2 and a.shape[1] == N:
+            return a
+        raise ValueError("sense2d: %s have shape %r; they are a (C, ny, nx) = (C, %d, %d) array, a (C, N) = (C, %d) array or a sequence of C planes"
+                         % (what, a.shape, ny, nx, N))
+
+    def plane(a, what):
+        if a.ndim == 2 and a.shape == (ny, nx):
+            a = a.reshape(-1, order="F")
+        if a.ndim != 1 or a.size != N:
+            raise ValueError("sense2d: %s has shape %r; a plane is a vector of nx ny = %d values or an (ny, nx) = (%d, %d) array" % (what, a.shape, N, ny, nx))
+        return a
+
+    def parts(v, kinds, what):
+        """one of the accepted forms, with values of the given dtype kinds -> (C, N)"""
+        refusal = "%s have to be %s" % (what, "complex numbers, or a pair (re, im) of real arrays" if kinds == "c" else "real numbers")
+        if isinstance(v, (list, tuple)):                     # a sequence of planes
+            if len(v) == 0:
+                raise ValueError("sense2d: %s are empty" % what)
+            return np.stack([plane(array(p, kinds, refusal), "plane %d of %s" % (i, what)) for i, p in enumerate(v)])
+        return planes(array(v, kinds, refusal), what)
+
+    def real(v):
+        try:
+            return np.asarray(v).dtype.kind in "iuf"
+        except (TypeError, ValueError):
+            return False
+
+    if isinstance(maps, (list, tuple)) and len(maps) == 2 and real(maps[0]) and real(maps[1]):
+        re, im = parts(maps[0], "iuf", "the real parts of the maps"), parts(maps[1], "iuf", "the imaginary parts of the maps")
+        if re.shape != im.shape:
+            raise ValueError("sense2d: the real parts are %d planes and the imaginary parts %d" % (re.shape[0], im.shape[0]))
+    else:
+        m = parts(maps, "c", "the maps")
+        re, im = m.real, m.imag
+    C = int(re.shape[0])
+    if C < 1 or C > SENSE2D_MAX_COILS:
+        raise ValueError("sense2d: the maps are C = %d planes; C has to be from 1 to %d" % (C, SENSE2D_MAX_COILS))
+    flat = np.concatenate([np.asarray(re, np.float64).reshape(-1), np.asarray(im, np.float64).reshape(-1)])
+    if not np.isfinite(flat).all():
+        raise ValueError("sense2d: the maps hold a non-finite value")
+    if 2 * L * C * N >= 2 ** 31:
+        raise ValueError("sense2d: L = %d images of %d x %d with C = %d coils; 2 L C nx ny has to stay below 2^31" % (L, nx, ny, C))
+    sz = [2 * L * C * N, 2 * L * N]
+    data = [nx, ny, L, C, flat]
+    return lambda row, col, nrows, ncols: [["sense2d", row, col, data], sz]
+
+
 WAVELET2D_MAX_TAPS = 16
 WAVELET2D_ORTHO_TOLERANCE = 1e-12
 

@@ -486,6 +486,13 @@ std::map<std::string, typename Factory<T>::BlockFactory>& Factory<T>::block_reg(
       const auto size = declared_size(d, 3, "BlockFFT2D: the data cells are { nx, ny, L } or { nx, ny, L, nrows, ncols }.");
       return BlockFFT2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), size.first, size.second);
     };
+    // the multi-coil Fourier operator: cells { nx, ny, L, C, maps (full vector: C real planes of nx ny values, then C imaginary planes) }
+    reg["sense2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
+      const auto size = declared_size(d, 5, "BlockSense2D: the data cells are { nx, ny, L, C, maps } or { nx, ny, L, C, maps, nrows, ncols }.");
+      const std::vector<double> maps = full_vector(d, 4, "BlockSense2D: the maps have to be a full vector of type single or double.");
+      return BlockSense2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), GetScalarFromCell(d, 3), maps, size.first,
+                                     size.second);
+    };
     // the orthogonal multi-level wavelet transform: cells { nx, ny, L, taps (full vector, the low-pass filter), levels }
     reg["wavelet2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
       const auto size = declared_size(d, 5, "BlockWavelet2D: the data cells are { nx, ny, L, taps, levels } or { nx, ny, L, taps, levels, nrows, ncols }.");

@@ -36,6 +36,7 @@ template <typename T> struct Api;
     static constexpr auto radon2d = prost_hip_radon2d_##S; \
     static constexpr auto sample2d = prost_hip_sample2d_##S; \
     static constexpr auto fft2d = prost_hip_fft2d_##S; \
+    static constexpr auto sense2d = prost_hip_sense2d_##S; \
     static constexpr auto wavelet2d = prost_hip_wavelet2d_##S; \
     static constexpr auto linop_sym_gradient2d = prost_hip_linop_sym_gradient2d_##S; \
     static constexpr auto linop_tensor_gradient2d = prost_hip_linop_tensor_gradient2d_##S; \

@@ -872,6 +872,81 @@ void BlockFFT2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
 template class BlockFFT2D<float>;
 template class BlockFFT2D<double>;
 
+// ---- the multi-coil Fourier operator of parallel MRI, without a matrix ----
+template <typename T>
+BlockSense2D<T>* BlockSense2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, double C, const std::vector<double>& maps, double declared_rows,
+                                         double declared_cols) {
+  const char* kName = "BlockSense2D";
+  for (const Named& v : {Named("nx", nx), Named("ny", ny)})
+    if (!(v.second >= 1) || v.second != std::floor(v.second) || v.second > fft2d::kMaxSide || !fft2d::IsSide((long)v.second))
+      Refuse(kName, v.first, " = ", v.second, " has to be a power of two from 1 to ", fft2d::kMaxSide, ".");
+  CheckBelowTwo31(kName, {{"L", L}});
+  CheckIntegers(kName, {{"C", C}}, sense2d::kMaxCoils, " coils; C has to be an integer from 1 to " + std::to_string(sense2d::kMaxCoils) + ".");
+  const double N = ny * nx, rows = 2 * L * C * N, cols = 2 * L * N;
+  if (rows >= kTwo31) Refuse(kName, "L = ", L, " images of ", nx, " x ", ny, " with C = ", C, " coils; 2 L C nx ny has to stay below 2^31.");
+  if ((double)maps.size() != 2 * C * N) Refuse(kName, "the maps hold ", maps.size(), " values, not 2 C = ", 2 * C, " planes of nx ny = ", N, ".");
+  CheckDeclaredSize(kName, declared_rows, declared_cols, rows, cols, "2 L C ny nx x 2 L ny nx");
+  std::unique_ptr<BlockSense2D<T>> b(new BlockSense2D<T>(row, col, (size_t)rows, (size_t)cols));
+  b->geometry_ = sense2d::MakeGeometry((long)ny, (long)nx, (long)L, (long)C, false);
+  b->table_ = fft2d::MakeTable<T>(fft2d::TableSize((int)ny, (int)nx));
+  b->maps_.resize(maps.size());
+  const size_t n = (size_t)N, coils = (size_t)C;
+  for (size_t i = 0; i < maps.size(); i++) {
+    const T t = (T)maps[i];                         // rounded once
+    if (!std::isfinite((double)t))
+      Refuse(kName, "value ", i % n, " of the ", i / n < coils ? "real" : "imaginary", " part of map ", (i / n) % coils, ", ", maps[i], ", is not finite", PrecisionStop<T>());
+    b->maps_[i] = t;
+  }
+  b->rows_.resize(coils);
+  for (size_t c = 0; c < coils; c++) b->rows_[c] = sense2d::RowBound<T>(b->maps_.data(), b->geometry_, 1.0, (int)c);
+  return b.release();
+}
+template <typename T>
+double BlockSense2D<T>::RowBoundOf(double alpha, size_t c) const {
+  std::lock_guard<std::mutex> lock(rows_lock_);
+  if (alpha != rows_alpha_) {
+    for (size_t k = 0; k < rows_.size(); k++) rows_[k] = sense2d::RowBound<T>(maps_.data(), geometry_, alpha, (int)k);
+    rows_alpha_ = alpha;
+  }
+  return rows_[c];
+}
+template <typename T>
+void BlockSense2D<T>::Initialize() { d_table_ = table_; d_maps_ = maps_; d_work_.resize(this->nrows(), (T)0); }
+template <typename T>
+void BlockSense2D<T>::Release() { d_table_.clear(); d_maps_.clear(); d_work_.clear(); }
+template <typename T>
+T BlockSense2D<T>::row_sum(size_t row, T alpha) const {
+  const sense2d::Geometry& g = geometry_;
+  const size_t image = (row / ((size_t)g.ny * (size_t)g.nx)) % ((size_t)g.planes * (size_t)g.coils);      // j = l C + c of the real or the imaginary plane
+  return (T)RowBoundOf((double)alpha, image % (size_t)g.coils);
+}
+template <typename T>
+T BlockSense2D<T>::col_sum(size_t col, T alpha) const {
+  return (T)sense2d::ColBound<T>(maps_.data(), geometry_, (double)alpha, col % ((size_t)geometry_.ny * (size_t)geometry_.nx));
+}
+template <typename T>
+void BlockSense2D<T>::row_sums(T* out, T alpha) const {
+  const sense2d::Geometry& g = geometry_;
+  std::vector<double> bound((size_t)g.coils);
+  for (int c = 0; c < g.coils; c++) bound[(size_t)c] = RowBoundOf((double)alpha, (size_t)c);
+  AddPlaneConstants(out, (size_t)g.ny * (size_t)g.nx, 2 * (size_t)g.planes * (size_t)g.coils, [&](size_t plane) { return (T)bound[plane % (size_t)g.coils]; });
+}
+template <typename T>
+void BlockSense2D<T>::col_sums(T* out, T alpha) const {
+  const sense2d::Geometry& g = geometry_;
+  AddPlaneSums(out, (size_t)g.ny * (size_t)g.nx, 2 * (size_t)g.planes, [&](size_t p) { return sense2d::ColBound<T>(maps_.data(), g, (double)alpha, p); });
+}
+template <typename T>
+void BlockSense2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
+  if (d_table_.size() != table_.size() || d_maps_.size() != maps_.size() || d_work_.size() != this->nrows()) throw Exception("BlockSense2D used before Initialize().");
+  static_assert(sizeof(prost_hip_sense2d_geometry) == sizeof(sense2d::Geometry), "records of prost_hip.h");
+  const sense2d::Geometry g = Directed(geometry_, transpose);
+  CheckHip(Api<T>::sense2d(reinterpret_cast<const prost_hip_sense2d_geometry*>(&g), d_table_.data(), d_maps_.data(), d_work_.data(), r, x, acc ? 1 : 0, CurrentStream()),
+           "sense2d");
+}
+template class BlockSense2D<float>;
+template class BlockSense2D<double>;
+
 // ---- the orthogonal multi-level wavelet transform, without a matrix ----
 template <typename T>
 BlockWavelet2D<T>* BlockWavelet2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, const std::vector<double>& taps, double levels,

@@ -32,75 +32,14 @@
 // the grid's y axis.  No scratch, no atomics: a repeated call repeats its bits.  Resource table: docs/rounds/r25.md.
 #include <cstring>
 
-#include "common.hpp"
-#include "prost/linop/fft2d.hpp"
+#include "fft2d_tile.hpp"
 
 namespace prost_hip {
 
-namespace f2d = prost::fft2d;
-
 static_assert(sizeof(f2d::Geometry) == sizeof(prost_hip_fft2d_geometry), "geometry record");
-
-constexpr unsigned kFftMaxPlaneGrid = 65535;
-enum { kToWork = 0, kFinal = 1, kFinalAdd = 2 };
-
-constexpr int kFftSmallTile = 2048;                          ///< complex values: 16 KiB of LDS in fp32, 32 KiB in fp64; one longest line
-template <class T> struct FftTile {
-  static constexpr int kLarge = 32768 / (int)sizeof(T);     ///< complex values of the large tile: 64 KiB of LDS
-};
-constexpr int kFftSlab = 16;                                 ///< lines the x pass wants side by side: 64 contiguous bytes per row in fp32
-static_assert(kFftSmallTile >= f2d::kMaxSide && FftTile<double>::kLarge >= 2 * f2d::kMaxSide, "a tile holds the longest line, the large one two");
-
-/// LDS address of element e of line b
-template <bool XPASS> __device__ __forceinline__ int fft_at(int b, int e, int lb, int pitch) { return XPASS ? (e << lb) + b : b * pitch + e; }
-
-/// the stages of B = 2^lb lines of m = 2^lm points held in re / im
-template <class T, bool INV, bool XPASS, int ELEMS>
-__device__ __forceinline__ void fft_tile_stages(T* re, T* im, int lm, int lb, int pitch, const T* __restrict__ table, int ltab) {
-  constexpr int kPer = ELEMS / 2 / kBlock;                   // butterflies of a lane per stage
-  if (lm == 0) return;
-  const int nb = 1 << (lm + lb - 1), half = 1 << (lm - 1);
-  for (int lh = 0; lh < lm; lh++) {
-    const int h = 1 << lh;
-    f2d::Cx<T> a[kPer], b[kPer];
-#pragma unroll
-    for (int u = 0; u < kPer; u++) {
-      const int idx = (int)threadIdx.x + u * kBlock;
-      if (idx < nb) {
-        const int line = XPASS ? (idx & ((1 << lb) - 1)) : (idx >> (lm - 1)), j = XPASS ? (idx >> lb) : (idx & (half - 1));
-        const int ia = fft_at<XPASS>(line, j, lb, pitch), ib = fft_at<XPASS>(line, j + half, lb, pitch);
-        a[u].re = re[ia]; a[u].im = im[ia]; b[u].re = re[ib]; b[u].im = im[ib];
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < kPer; u++) {
-      const int idx = (int)threadIdx.x + u * kBlock;
-      if (idx < nb) {
-        const int line = XPASS ? (idx & ((1 << lb) - 1)) : (idx >> (lm - 1)), j = XPASS ? (idx >> lb) : (idx & (half - 1));
-        const int k = j & (h - 1), e0 = k + ((j >> lh) << (lh + 1));
-        const int w = k << (ltab - lh - 1);                  // below half the table
-        const f2d::Cx<T> t = f2d::Twiddled<T, INV>(b[u], k, h, table[2 * w], table[2 * w + 1]);
-        const int o0 = fft_at<XPASS>(line, e0, lb, pitch), o1 = fft_at<XPASS>(line, e0 + h, lb, pitch);
-        re[o0] = a[u].re + t.re; im[o0] = a[u].im + t.im;
-        re[o1] = a[u].re - t.re; im[o1] = a[u].im - t.im;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-template <class T, int MODE> __device__ __forceinline__ void fft_store(T* o, T v, T s) {
-  if (MODE == kToWork) { *o = v; return; }
-  const T scaled = v * s;
-  *o = MODE == kFinalAdd ? *o + scaled : scaled;
-}
 
 /// XPASS: lines of nx points at stride ny, the tile's lines are y0 .. y0 + B - 1; else lines of ny contiguous points, the tile's lines are
 /// columns x0 .. x0 + B - 1
-/// W values of T, 16 bytes when W > 1: one global access of a lane
-template <class T, int W> struct alignas(sizeof(T) * W) FftPack { T v[W]; };
-
 /// blockIdx.x: a tile of 2^lb lines.  W: values a lane moves per global access, 1 or 16 / sizeof(T); the launcher picks 16 bytes when src and
 /// dst are 16-byte aligned and a contiguous run of the tile (a line of the y pass, the B rows of a slab) holds at least W values
 template <class T, bool INV, bool XPASS, int MODE, int ELEMS, int W>
@@ -139,31 +78,22 @@ __global__ void __launch_bounds__(kBlock) fft2d_pass_kernel(T* dst, const T* src
 
 template <class T, bool INV, bool XPASS, int MODE, int ELEMS>
 static void launch_fft2d_tile(T* dst, const T* src, const f2d::Geometry& g, const T* table, hipStream_t stream) {
-  const int tile = ELEMS;
-  const int m = XPASS ? g.nx : g.ny, lines = XPASS ? g.ny : g.nx;
-  const int cap = (!XPASS && m < 64) ? tile / 2 : tile;            // short contiguous lines are pitched at 3 m / 2
-  const int pitch = (!XPASS && m < 64) ? m + m / 2 : m;
-  const int B = cap / m < lines ? cap / m : lines;
+  const FftTileShape t = fft_tile_shape<XPASS>(g, ELEMS);
   const unsigned planes = (unsigned)g.planes < kFftMaxPlaneGrid ? (unsigned)g.planes : kFftMaxPlaneGrid;
-  const dim3 grid((unsigned)(lines / B), planes), block(kBlock);
+  const dim3 grid(t.tiles, planes), block(kBlock);
   const T s = f2d::Scale<T>(g.ny, g.nx);
-  const int lm = f2d::Log2(m), lb = f2d::Log2(B), ltab = f2d::Log2(f2d::TableSize(g.ny, g.nx));
-  // 16 bytes per lane where the pointers allow: every plane and every run then starts on a multiple of 16 bytes, since a run's length (a
-  // power of two, at least kWide) divides every offset in front of it
   constexpr int kWide = 16 / (int)sizeof(T);
-  const bool wide = (XPASS ? B : m) >= kWide && (reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) % 16 == 0;
-  if (wide) PH_LAUNCH((fft2d_pass_kernel<T, INV, XPASS, MODE, ELEMS, kWide>), grid, block, 0, stream, dst, src, g, table, s, lm, lb, pitch, ltab);
-  else PH_LAUNCH((fft2d_pass_kernel<T, INV, XPASS, MODE, ELEMS, 1>), grid, block, 0, stream, dst, src, g, table, s, lm, lb, pitch, ltab);
+  if (fft_tile_wide<T>(t, {dst, src})) PH_LAUNCH((fft2d_pass_kernel<T, INV, XPASS, MODE, ELEMS, kWide>), grid, block, 0, stream, dst, src, g, table, s, t.lm, t.lb, t.pitch, t.ltab);
+  else PH_LAUNCH((fft2d_pass_kernel<T, INV, XPASS, MODE, ELEMS, 1>), grid, block, 0, stream, dst, src, g, table, s, t.lm, t.lb, t.pitch, t.ltab);
 }
 
-/// the y pass takes small tiles: its lines are contiguous, and 5 to 10 workgroups on a CU overlap one tile's loads with another's stages.
-/// The x pass takes the small tile while it holds kFftSlab lines (nx <= 128), else the large one
+/// the tile of a pass: fft_small_tile (fft2d_tile.hpp)
 template <class T, bool INV, bool XPASS, int MODE>
 static void launch_fft2d_pass(T* dst, const T* src, const f2d::Geometry& g, const T* table, hipStream_t stream) {
   if constexpr (!XPASS) {
     launch_fft2d_tile<T, INV, XPASS, MODE, kFftSmallTile>(dst, src, g, table, stream);
   } else {
-    if (g.nx * kFftSlab <= kFftSmallTile) launch_fft2d_tile<T, INV, XPASS, MODE, kFftSmallTile>(dst, src, g, table, stream);
+    if (fft_small_tile<XPASS>(g)) launch_fft2d_tile<T, INV, XPASS, MODE, kFftSmallTile>(dst, src, g, table, stream);
     else launch_fft2d_tile<T, INV, XPASS, MODE, FftTile<T>::kLarge>(dst, src, g, table, stream);
   }
 }
@@ -182,6 +112,25 @@ static void launch_fft2d_dir(const f2d::Geometry& g, const T* table, T* work, T*
     else launch_fft2d_pass<T, INV, true, kFinal>(res, rhs, g, table, s);
   }
 }
+
+template <class T, bool INV, bool XPASS>
+static void launch_fft2d_mode(int mode, T* dst, const T* src, const f2d::Geometry& g, const T* table, hipStream_t s) {
+  if constexpr (!XPASS)                                            // the x pass is always the last one
+    if (mode == kToWork) { launch_fft2d_pass<T, INV, XPASS, kToWork>(dst, src, g, table, s); return; }
+  if (mode == kFinal) launch_fft2d_pass<T, INV, XPASS, kFinal>(dst, src, g, table, s);
+  else launch_fft2d_pass<T, INV, XPASS, kFinalAdd>(dst, src, g, table, s);
+}
+/// one pass on its own, for kernels_linop_sense2d.hip (fft2d_tile.hpp): the launches above, nothing else.  The x pass is always the last
+/// pass and has no instance that writes the work buffer: that combination, and a mode that is none of the three, is refused (false, no launch)
+template <class T>
+bool fft2d_launch_pass(bool inverse, bool xpass, int mode, T* dst, const T* src, const f2d::Geometry& g, const T* table, hipStream_t s) {
+  if ((mode != kToWork && mode != kFinal && mode != kFinalAdd) || (xpass && mode == kToWork)) return false;
+  if (inverse) { if (xpass) launch_fft2d_mode<T, true, true>(mode, dst, src, g, table, s); else launch_fft2d_mode<T, true, false>(mode, dst, src, g, table, s); }
+  else { if (xpass) launch_fft2d_mode<T, false, true>(mode, dst, src, g, table, s); else launch_fft2d_mode<T, false, false>(mode, dst, src, g, table, s); }
+  return true;
+}
+template bool fft2d_launch_pass<float>(bool, bool, int, float*, const float*, const f2d::Geometry&, const float*, hipStream_t);
+template bool fft2d_launch_pass<double>(bool, bool, int, double*, const double*, const f2d::Geometry&, const double*, hipStream_t);
 
 template <class T>
 static int launch_fft2d(const prost_hip_fft2d_geometry* geometry, const T* table, T* work, T* res, const T* rhs, int accumulate, void* stream) {
