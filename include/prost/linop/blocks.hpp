@@ -8,6 +8,7 @@
 #include "prost/linop/block.hpp"
 #include "prost/linop/conv2d.hpp"
 #include "prost/linop/conv2d_strided.hpp"
+#include "prost/linop/fanbeam2d.hpp"
 #include "prost/linop/fft2d.hpp"
 #include "prost/linop/hessian2d.hpp"
 #include "prost/linop/radon2d.hpp"
@@ -309,6 +310,34 @@ class BlockRadon2D : public ProductBlock<T> {
   virtual void Product(T* res, const T* rhs, bool transpose, bool accumulate);
   radon2d::Geometry geometry_;
   std::vector<T> table_;                   ///< the per-angle table as it is uploaded
+  device_vector<T> d_table_;
+};
+
+/// the fan-beam projector of tomography (a point source, a flat or an equiangular detector; Joseph's method) and its exact transpose,
+/// without a matrix: L column-major planes of ny x nx onto L sinograms of na views x ndet bins.  L na ndet rows by L ny nx columns.
+/// Geometry, tables, arithmetic and the candidate window of the adjoint: prost/linop/fanbeam2d.hpp.  No describe(): the block runs on
+/// the generic paths.  Only the tables, five numbers per view, two per bin and ten more, are stored.
+template <typename T>
+class BlockFanbeam2D : public ProductBlock<T> {
+ public:
+  /// checks every argument (messages start with "BlockFanbeam2D: "); declared_rows / declared_cols < 0: no size was declared
+  static BlockFanbeam2D<T>* Create(size_t row, size_t col, double nx, double ny, double L, const std::vector<double>& angles, double source_distance,
+                                   double detector_distance, double ndet, double spacing, double shift, const std::string& detector, double declared_rows = -1,
+                                   double declared_cols = -1);
+  virtual void Initialize();
+  virtual void Release();
+  virtual T row_sum(size_t row, T alpha) const;
+  virtual T col_sum(size_t col, T alpha) const;
+  virtual void row_sums(T* out, T alpha) const;              ///< one plane enumerated once on several host threads, then repeated for every plane
+  virtual void col_sums(T* out, T alpha) const;
+  virtual size_t gpu_mem_amount() const { return table_.size() * sizeof(T); }
+  const fanbeam2d::Geometry& geometry() const { return geometry_; }
+
+ protected:
+  BlockFanbeam2D(size_t row, size_t col, size_t nrows, size_t ncols) : ProductBlock<T>(row, col, nrows, ncols) {}
+  virtual void Product(T* res, const T* rhs, bool transpose, bool accumulate);
+  fanbeam2d::Geometry geometry_;
+  std::vector<T> table_;                   ///< the three tables as they are uploaded
   device_vector<T> d_table_;
 };
 

@@ -288,6 +288,34 @@ typedef struct prost_hip_radon2d_geometry {
 } prost_hip_radon2d_geometry;
 int prost_hip_radon2d_f32(const prost_hip_radon2d_geometry* geometry, const float* table, float* res, const float* rhs, int accumulate, void* stream);
 int prost_hip_radon2d_f64(const prost_hip_radon2d_geometry* geometry, const double* table, double* res, const double* rhs, int accumulate, void* stream);
+/* BlockFanbeam2D (additions; ABI version unchanged; kernels_linop_fanbeam2d.hip, arithmetic, order of operations, table layout and
+ * the candidate window of the adjoint: prost/linop/fanbeam2d.hpp): the fan-beam projector K (a point source, a flat or an equiangular
+ * detector; Joseph's method) of `planes` column-major image planes of ny x nx onto `planes` sinograms of na views x ndet bins (bin d of
+ * view a at d + a ndet), and its exact transpose:
+ *   transpose == 0:  res(a, d) = sum over the driving lines t of (c w0) rhs(t, i0) + (c w1) rhs(t, i0 + 1)       rhs: images
+ *   transpose != 0:  res(t, i) = sum over views and candidate bins of the same entries times rhs(a, d)           rhs: sinograms
+ * The geometry record is a HOST pointer, read before the call returns.  table: one array of T in device memory, already rounded to T
+ * (prost::fanbeam2d::MakeTable makes it): na rows { cos, sin, sx, sy, axis }, then ndet rows { sin gamma, cos gamma }, then the
+ * inverse map { k0, k1, lo, hi, a_1 .. a_6 } -- na VIEW_WIDTH + ndet BIN_WIDTH + INVERSE_WIDTH values; they are trusted (any table
+ * gives in-bounds accesses).  m is the margin of the adjoint's candidate window.  accumulate != 0 stores res + value instead of
+ * value; a ray that misses the image and a pixel no ray samples store 0.  Any alignment of T is accepted.  Aliasing: res and rhs must
+ * NOT overlap, and the table overlaps neither.  No atomics: a call repeats its bits.  No allocation, copy or synchronisation.  Refused
+ * without a launch: a null pointer, nx or ny outside 1 .. 8192, na outside 1 .. 4096, ndet or planes below 1, ndet above 2^31 - 1025,
+ * m outside 1 .. MAX_MARGIN, a sinogram of 2^31 elements or more. */
+#define PROST_HIP_FANBEAM2D_VIEW_WIDTH 5
+#define PROST_HIP_FANBEAM2D_BIN_WIDTH 2
+#define PROST_HIP_FANBEAM2D_INVERSE_WIDTH 10
+#define PROST_HIP_FANBEAM2D_MAX_MARGIN 5
+typedef struct prost_hip_fanbeam2d_geometry {
+  int32_t ny, nx;       /* image plane */
+  int32_t ndet, na;     /* bins per view, views */
+  int32_t planes;
+  int32_t m;            /* margin of the candidate window */
+  int32_t transpose;
+  int32_t reserved;     /* 0 */
+} prost_hip_fanbeam2d_geometry;
+int prost_hip_fanbeam2d_f32(const prost_hip_fanbeam2d_geometry* geometry, const float* table, float* res, const float* rhs, int accumulate, void* stream);
+int prost_hip_fanbeam2d_f64(const prost_hip_fanbeam2d_geometry* geometry, const double* table, double* res, const double* rhs, int accumulate, void* stream);
 /* BlockSample2D (additions; ABI version unchanged; kernels_linop_sample2d.hip, arithmetic, order of operations and the bucket tables
  * of the adjoint: prost/linop/sample2d.hpp): bilinear resampling K of `planes` column-major image planes of ny x nx at m positions per
  * plane (sample i of plane c at i + c m), zero padding, and its exact transpose.  With j0 = floor(fx), ax = fx - j0, bx = 1 - ax and

@@ -302,6 +302,105 @@ def radon2d(nx, ny, L, angles, ndet=None, spacing=1.0, shift=0.0):
     return lambda row, col, nrows, ncols: [["radon2d", row, col, data], sz]
 
 
+FANBEAM2D_MAX_SIDE = 8192
+FANBEAM2D_MAX_VIEWS = 4096
+FANBEAM2D_MAX_FAN_DEGREES = 30.0
+FANBEAM2D_MAX_MARGIN = 5
+FANBEAM2D_SLACK = 0.25
+
+
+def _fanbeam2d_number(name, v):
+    if isinstance(v, bool) or not isinstance(v, _NUMBER):
+        raise ValueError("fanbeam2d: %s = %r is not a number" % (name, v))
+    return float(v)
+
+
+def _fanbeam2d_scanner(nx, ny, source_distance, detector_distance, spacing, detector):
+    """the checks fanbeam2d and fanbeam2d_ndet share -> (R, D, spacing, curved)"""
+    R = _fanbeam2d_number("source_distance", source_distance)
+    D = R if detector_distance is None else _fanbeam2d_number("detector_distance", detector_distance)
+    spacing = _fanbeam2d_number("spacing", spacing)
+    if not isinstance(detector, str) or detector not in ("flat", "curved"):
+        raise ValueError("fanbeam2d: unknown detector %r (flat or curved)" % (detector,))
+    if not 0.5 <= spacing <= 8:
+        raise ValueError("fanbeam2d: spacing = %r has to be from 0.5 to 8" % (spacing,))
+    if not (np.isfinite(R) and R > 0):
+        raise ValueError("fanbeam2d: source_distance = %r has to be positive and finite" % (R,))
+    if not (np.isfinite(D) and D > 0):
+        raise ValueError("fanbeam2d: detector_distance = %r has to be positive and finite" % (D,))
+    closest = math.hypot(nx, ny) / 2.0 + 1.0
+    if not R >= closest:
+        raise ValueError("fanbeam2d: source_distance = %r puts the source inside the image's circumscribed circle or less than a pixel off it; "
+                         "it has to be at least %r" % (R, closest))
+    return R, D, spacing, detector == "curved"
+
+
+def fanbeam2d_ndet(nx, ny, source_distance, detector_distance=None, spacing=1.0, detector="flat"):
+    """the default detector length of fanbeam2d: the smallest odd count of bins whose outermost rays pass outside the image's
+    circumscribed circle at every view, 2 ceil(u / spacing) + 1 with u = D tan(asin(hd / R)) on a flat detector and D asin(hd / R) on a
+    curved one, hd = hypot(nx, ny) / 2"""
+    nx, ny = _integer("fanbeam2d", "nx", nx, FANBEAM2D_MAX_SIDE), _integer("fanbeam2d", "ny", ny, FANBEAM2D_MAX_SIDE)
+    R, D, spacing, curved = _fanbeam2d_scanner(nx, ny, source_distance, detector_distance, spacing, detector)
+    need = math.asin(math.hypot(nx, ny) / 2.0 / R)
+    u = D * need if curved else D * math.tan(need)
+    return 2 * int(math.ceil(u / spacing)) + 1
+
+
+def fanbeam2d(nx, ny, L, angles, source_distance, detector_distance=None, ndet=None, spacing=1.0, shift=0.0, detector="flat"):
+    """The fan-beam projector of tomography (a point source, Joseph's method), applied without a matrix, and its exact transpose.
+    Domain and range as radon2d: L column-major planes of ny x nx, element (y, x, c) at y + x ny + c nx ny; L sinograms, bin d of view
+    a of plane c at d + a ndet + c ndet na.  Pixel centres sit at X = x - (nx - 1) / 2, Y = y - (ny - 1) / 2.  At view beta (radians,
+    up to 4096) the detector axis is e = (cos, sin), the central ray n = (-sin, cos) and the source S = -R n, R = source_distance in
+    pixels, at least hypot(nx, ny) / 2 + 1.  Bin d sits at u_d = (d - (ndet - 1) / 2) spacing + shift along a detector at distance
+    D = detector_distance from the source (None: D = R, a virtual detector through the rotation centre); its ray leaves S at the fan
+    angle gamma_d = atan(u_d / D) (detector "flat") or u_d / D ("curved", equiangular) in direction sin(gamma) e + cos(gamma) n.  With
+    D = R -> infinity the flat geometry tends to radon2d(.., spacing, shift).  ndet: None for fanbeam2d_ndet(..); 0.5 <= spacing <= 8.
+    Per view the rays are marched over the rows if |cos| >= |sin| and over the columns otherwise, interpolated linearly along the other
+    axis; no ray may be more than 30 degrees off the central one.  The adjoint gathers, per pixel and view, a window of 2 m + 2
+    candidate bins, m = ceil(D / (R - hc) / (spacing cos(gamma_max)) + 1 / 4) with hc = hypot(nx - 1, ny - 1) / 2, and m <= 5 is
+    required: a source at R >= hypot(nx, ny) with the default detector always passes.  Stored: five numbers per view, two per bin."""
+    nx, ny = _integer("fanbeam2d", "nx", nx, FANBEAM2D_MAX_SIDE), _integer("fanbeam2d", "ny", ny, FANBEAM2D_MAX_SIDE)
+    L = _integer("fanbeam2d", "L", L)
+    if ndet is not None:
+        ndet = _integer("fanbeam2d", "ndet", ndet)
+    try:
+        angles = np.array(angles, dtype=np.float64, copy=True)
+    except (TypeError, ValueError):
+        raise ValueError("fanbeam2d: the angles have to be a vector of numbers")
+    if angles.ndim == 0:
+        angles = angles.reshape(1)
+    if angles.ndim != 1 or angles.size == 0:
+        raise ValueError("fanbeam2d: the angles have to be a non-empty vector, got shape %r" % (angles.shape,))
+    if angles.size > FANBEAM2D_MAX_VIEWS:
+        raise ValueError("fanbeam2d: %d views, up to %d are supported" % (angles.size, FANBEAM2D_MAX_VIEWS))
+    if not np.isfinite(angles).all():
+        raise ValueError("fanbeam2d: the angles hold a non-finite value")
+    shift = _fanbeam2d_number("shift", shift)
+    if not np.isfinite(shift):
+        raise ValueError("fanbeam2d: shift = %r has to be finite" % (shift,))
+    R, D, spacing, curved = _fanbeam2d_scanner(nx, ny, source_distance, detector_distance, spacing, detector)
+    if ndet is None:
+        ndet = fanbeam2d_ndet(nx, ny, R, D, spacing, detector)
+    if ndet > 2 ** 31 - 1025:
+        raise ValueError("fanbeam2d: ndet = %d has to be below 2^31 - 1024" % ndet)
+    if ndet * angles.size >= 2 ** 31:
+        raise ValueError("fanbeam2d: a sinogram of %d elements; it has to stay below 2^31" % (ndet * angles.size))
+    fan = 0.0
+    for d in (0, ndet - 1):
+        u = (d - (ndet - 1) / 2.0) * spacing + shift
+        fan = max(fan, abs(u / D if curved else math.atan2(u, D)))
+    if not math.degrees(fan) <= FANBEAM2D_MAX_FAN_DEGREES:
+        raise ValueError("fanbeam2d: the outermost ray is %.6g degrees off the central ray; half fans up to %g degrees are supported"
+                         % (math.degrees(fan), FANBEAM2D_MAX_FAN_DEGREES))
+    margin = math.ceil(D / (R - math.hypot(nx - 1, ny - 1) / 2.0) / (spacing * math.cos(fan)) + FANBEAM2D_SLACK)
+    if margin > FANBEAM2D_MAX_MARGIN:
+        raise ValueError("fanbeam2d: the candidate window of the adjoint needs a margin of %d bins, up to %d are supported (a source farther away, "
+                         "a detector nearer to it or a larger spacing)" % (margin, FANBEAM2D_MAX_MARGIN))
+    sz = [L * angles.size * ndet, L * ny * nx]
+    data = [nx, ny, L, angles, R, D, ndet, spacing, shift, detector]
+    return lambda row, col, nrows, ncols: [["fanbeam2d", row, col, data], sz]
+
+
 SAMPLE2D_MAX_SIDE = 16384
 
 

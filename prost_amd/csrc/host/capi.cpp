@@ -474,6 +474,15 @@ std::map<std::string, typename Factory<T>::BlockFactory>& Factory<T>::block_reg(
       return BlockRadon2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), angles, GetScalarFromCell(d, 4),
                                      GetScalarFromCell(d, 5), GetScalarFromCell(d, 6), size.first, size.second);
     };
+    // the fan-beam projector: cells { nx, ny, L, angles (full vector), source_distance, detector_distance, ndet, spacing, shift, detector }
+    reg["fanbeam2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
+      const auto size = declared_size(d, 10, "BlockFanbeam2D: the data cells are { nx, ny, L, angles, source_distance, detector_distance, ndet, spacing, shift, detector } or { nx, ny, L, angles, source_distance, detector_distance, ndet, spacing, shift, detector, nrows, ncols }.");
+      const std::vector<double> angles = full_vector(d, 3, "BlockFanbeam2D: the angles have to be a full vector of type single or double.");
+      if (!d->cells[9] || d->cells[9]->kind != PROST_VALUE_STRING) throw Exception("BlockFanbeam2D: the detector has to be a string (flat or curved).");
+      return BlockFanbeam2D<T>::Create(row, col, GetScalarFromCell(d, 0), GetScalarFromCell(d, 1), GetScalarFromCell(d, 2), angles, GetScalarFromCell(d, 4),
+                                       GetScalarFromCell(d, 5), GetScalarFromCell(d, 6), GetScalarFromCell(d, 7), GetScalarFromCell(d, 8), d->cells[9]->str, size.first,
+                                       size.second);
+    };
     // bilinear resampling: cells { nx, ny, L, x, y (full vectors of the same length) }
     reg["sample2d"] = [](size_t row, size_t col, const prost_value* d) -> Block<T>* {
       const auto size = declared_size(d, 5, "BlockSample2D: the data cells are { nx, ny, L, x, y } or { nx, ny, L, x, y, nrows, ncols }.");

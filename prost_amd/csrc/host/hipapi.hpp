@@ -34,6 +34,7 @@ template <typename T> struct Api;
     static constexpr auto conv2d = prost_hip_conv2d_##S; \
     static constexpr auto conv2d_strided = prost_hip_conv2d_strided_##S; \
     static constexpr auto radon2d = prost_hip_radon2d_##S; \
+    static constexpr auto fanbeam2d = prost_hip_fanbeam2d_##S; \
     static constexpr auto sample2d = prost_hip_sample2d_##S; \
     static constexpr auto fft2d = prost_hip_fft2d_##S; \
     static constexpr auto sense2d = prost_hip_sense2d_##S; \

@@ -767,6 +767,85 @@ void BlockRadon2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
 template class BlockRadon2D<float>;
 template class BlockRadon2D<double>;
 
+// ---- the fan-beam projector of tomography, without a matrix ----
+template <typename T>
+BlockFanbeam2D<T>* BlockFanbeam2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, const std::vector<double>& angles, double source_distance,
+                                             double detector_distance, double ndet, double spacing, double shift, const std::string& detector, double declared_rows,
+                                             double declared_cols) {
+  namespace f2d = fanbeam2d;
+  const char* kName = "BlockFanbeam2D";
+  CheckIntegers(kName, {{"nx", nx}, {"ny", ny}}, f2d::kMaxSide, " has to be an integer from 1 to " + std::to_string(f2d::kMaxSide) + ".");
+  CheckBelowTwo31(kName, {{"L", L}});
+  if (angles.empty()) Refuse(kName, "the angles are empty.");
+  if (angles.size() > (size_t)f2d::kMaxViews) Refuse(kName, angles.size(), " views, up to ", f2d::kMaxViews, " are supported.");
+  CheckFinite(kName, angles, "the angles hold");
+  if (detector != "flat" && detector != "curved") Refuse(kName, "unknown detector '", detector, "' (flat or curved).");
+  if (!(spacing >= 0.5 && spacing <= 8)) Refuse(kName, "spacing = ", spacing, " has to be from 0.5 to 8.");
+  if (!std::isfinite(shift)) Refuse(kName, "shift = ", shift, " has to be finite.");
+  if (!(source_distance > 0) || !std::isfinite(source_distance)) Refuse(kName, "source_distance = ", source_distance, " has to be positive and finite.");
+  if (!(detector_distance > 0) || !std::isfinite(detector_distance)) Refuse(kName, "detector_distance = ", detector_distance, " has to be positive and finite.");
+  CheckIntegers(kName, {{"ndet", ndet}}, (double)f2d::kMaxBins, " has to be a positive integer below 2^31 - 1024.");
+  const double na = (double)angles.size();
+  if (ndet * na >= kTwo31) Refuse(kName, "a sinogram of ", ndet * na, " elements; it has to stay below 2^31.");
+  const double rows = L * na * ndet, cols = L * ny * nx;
+  CheckDeclaredSize(kName, declared_rows, declared_cols, rows, cols, "L na ndet x L ny nx");
+  const f2d::Scanner s = {(long)ny, (long)nx, (long)ndet, source_distance, detector_distance, spacing, shift, detector == "curved"};
+  const double closest = f2d::HalfDiagonal(s.nx, s.ny) + 1;
+  if (!(source_distance >= closest))
+    Refuse(kName, "source_distance = ", source_distance, " puts the source inside the image's circumscribed circle or less than a pixel off it; it has to be at least ", closest, ".");
+  const double fan = f2d::MaxFanAngle(s) * (180 / 3.14159265358979323846);
+  if (!(fan <= f2d::kMaxFanDegrees)) Refuse(kName, "the outermost ray is ", fan, " degrees off the central ray; half fans up to ", f2d::kMaxFanDegrees, " degrees are supported.");
+  const double margin = f2d::MarginOf(s);
+  if (!(margin <= f2d::kMaxMargin))
+    Refuse(kName, "the candidate window of the adjoint needs a margin of ", margin, " bins, up to ", f2d::kMaxMargin,
+           " are supported (a source farther away, a detector nearer to it or a larger spacing).");
+  if (!(f2d::Slack<T>(s) <= f2d::kSlack)) Refuse(kName, "source_distance = ", source_distance, " is too far for the candidate window of the adjoint", PrecisionStop<T>());
+  std::unique_ptr<BlockFanbeam2D<T>> b(new BlockFanbeam2D<T>(row, col, (size_t)rows, (size_t)cols));
+  b->geometry_ = f2d::MakeGeometry(s, (long)L, (long)angles.size(), false);
+  b->table_ = f2d::MakeTable<T>(s, angles);
+  for (T v : b->table_)
+    if (!std::isfinite(v)) Refuse(kName, "the tables are not finite", PrecisionStop<T>());
+  return b.release();
+}
+template <typename T>
+void BlockFanbeam2D<T>::Initialize() { d_table_ = table_; }
+template <typename T>
+void BlockFanbeam2D<T>::Release() { d_table_.clear(); }
+template <typename T>
+T BlockFanbeam2D<T>::row_sum(size_t row, T alpha) const {
+  const fanbeam2d::Geometry& g = geometry_;
+  const Pixel bin(row % ((size_t)g.ndet * (size_t)g.na), g.ndet);      // bin d of view a at d + a ndet
+  return (T)fanbeam2d::RowSum<T>(table_.data(), g, (double)alpha, bin.x, bin.y);
+}
+template <typename T>
+T BlockFanbeam2D<T>::col_sum(size_t col, T alpha) const {
+  const fanbeam2d::Geometry& g = geometry_;
+  const Pixel at(col % ((size_t)g.ny * (size_t)g.nx), g.ny);
+  return (T)fanbeam2d::ColSum<T>(table_.data(), g, (double)alpha, at.y, at.x);
+}
+// the sums of one plane are enumerated on several host threads: a ray costs max(nx, ny) steps, a pixel na (2 m + 2) prologues
+template <typename T>
+void BlockFanbeam2D<T>::row_sums(T* out, T alpha) const {
+  const fanbeam2d::Geometry& g = geometry_;
+  const size_t n = (size_t)g.ndet * (size_t)g.na;
+  AddPlaneSums(out, n, (size_t)g.planes, [&](size_t p) { return row_sum(p, alpha); }, ParallelChunks(n * (size_t)std::max(g.nx, g.ny)));
+}
+template <typename T>
+void BlockFanbeam2D<T>::col_sums(T* out, T alpha) const {
+  const fanbeam2d::Geometry& g = geometry_;
+  const size_t n = (size_t)g.ny * (size_t)g.nx;
+  AddPlaneSums(out, n, (size_t)g.planes, [&](size_t p) { return col_sum(p, alpha); }, ParallelChunks(n * (size_t)g.na * (size_t)(2 * g.m + 2) * 4));
+}
+template <typename T>
+void BlockFanbeam2D<T>::Product(T* r, const T* x, bool transpose, bool acc) {
+  if (d_table_.size() != table_.size()) throw Exception("BlockFanbeam2D used before Initialize().");
+  static_assert(sizeof(prost_hip_fanbeam2d_geometry) == sizeof(fanbeam2d::Geometry), "records of prost_hip.h");
+  const fanbeam2d::Geometry g = Directed(geometry_, transpose);
+  CheckHip(Api<T>::fanbeam2d(reinterpret_cast<const prost_hip_fanbeam2d_geometry*>(&g), d_table_.data(), r, x, acc ? 1 : 0, CurrentStream()), "fanbeam2d");
+}
+template class BlockFanbeam2D<float>;
+template class BlockFanbeam2D<double>;
+
 // ---- bilinear resampling at arbitrary positions, without a matrix ----
 template <typename T>
 BlockSample2D<T>* BlockSample2D<T>::Create(size_t row, size_t col, double nx, double ny, double L, const std::vector<double>& x, const std::vector<double>& y,
