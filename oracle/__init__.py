@@ -75,6 +75,7 @@ def lib():
         L.orc_csr_spmv_acc.argtypes = [i32, vp, vp, i32, vp, vp, vp]
         L.orc_prox_elem.argtypes = [i32, i32, i32, vp, vp, vp, dbl, i32, sz, sz, i32, vp, vp]
         L.orc_prox_epi_quad.argtypes = [i32, vp, vp, sz, sz, vp, dbl, vp, vp, dbl]
+        L.orc_prox_ind_sum.argtypes = [i32, vp, vp, vp, vp, sz, sz, dbl, dbl, i32]
         L.orc_glibc_rand_fill.argtypes = [C.c_uint, sz, vp]
         L.orc_glibc_rand_fill.restype = None
         L.orc_linspace.argtypes = [dbl, dbl, i32, vp]
@@ -267,6 +268,17 @@ def prox_epi_quad(arg, count, dim, a, b, c):
     _chk(lib().orc_prox_epi_quad(_dt(arg.dtype), _p(res), _p(arg), count, dim,
                                  _p(a) if a.size > 1 else None, float(a[0]), _p(b),
                                  _p(c) if c.size > 1 else None, float(c[0])))
+    return res
+
+
+def prox_ind_sum(arg, tau_diag, inds, dim, total_sum, tau, invert_tau=False):
+    """ProxIndSumKernel over one index family (inds: count * dim positions in arg) with the step flag as given"""
+    arg = np.ascontiguousarray(arg)
+    tau_diag = np.ascontiguousarray(tau_diag, dtype=arg.dtype)
+    inds = np.ascontiguousarray(np.asarray(inds, dtype=np.uint64).ravel())
+    res = arg.copy()
+    _chk(lib().orc_prox_ind_sum(_dt(arg.dtype), _p(res), _p(arg), _p(tau_diag), _p(inds), inds.size // dim, dim, float(total_sum),
+                                float(tau), int(invert_tau)))
     return res
 
 

@@ -1627,6 +1627,13 @@ int orc_prox_epi_quad(int dtype, void* res, const void* arg, size_t count, size_
   else epi_quad_run<double>(mptr<double>(res), cptr<double>(arg), count, dim, cptr<double>(a_ptr), a_val, cptr<double>(b_ptr), cptr<double>(c_ptr), c_val);
   ORC_CATCH
 }
+int orc_prox_ind_sum(int dtype, void* res, const void* arg, const void* tau_diag, const size_t* inds, size_t count, size_t dim,
+                     double total_sum, double tau, int invert) {
+  ORC_TRY
+  if (dtype == 0) ind_sum_run<float>(mptr<float>(res), cptr<float>(arg), cptr<float>(tau_diag), inds, count, dim, (float)total_sum, (float)tau, invert != 0);
+  else ind_sum_run<double>(mptr<double>(res), cptr<double>(arg), cptr<double>(tau_diag), inds, count, dim, total_sum, tau, invert != 0);
+  ORC_CATCH
+}
 void orc_glibc_rand_fill(unsigned seed, size_t n, int32_t* out) {
   GlibcRand g(seed);
   for (size_t i = 0; i < n; i++) out[i] = g.next();

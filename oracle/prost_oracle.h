@@ -73,6 +73,10 @@ int orc_prox_elem(int dtype, int op, int fn, void* res, const void* arg, const v
 int orc_prox_epi_quad(int dtype, void* res, const void* arg, size_t count, size_t dim,
                       const void* a_ptr, double a_val, const void* b_ptr,
                       const void* c_ptr, double c_val);
+/* prox_ind_sum.cu:30-66 on ONE index family with the step flag as given (Prox::Eval reaches invert_tau = 1
+ * only under a Moreau wrap); res must hold a copy of arg, inds count*dim indices into it */
+int orc_prox_ind_sum(int dtype, void* res, const void* arg, const void* tau_diag, const size_t* inds,
+                     size_t count, size_t dim, double total_sum, double tau, int invert_tau);
 /* glibc rand() restated (TYPE_3 additive feedback); used by normest (problem.cu:435) */
 void orc_glibc_rand_fill(unsigned seed, size_t n, int32_t* out);
 /* common.cu:33-46 ; out must hold num+1 doubles */

@@ -41,6 +41,12 @@ def available():
     return os.path.exists(_LIB_PATH)
 
 
+def has_nocoeff():
+    """True where the library is present AND holds the functors without coefficients (ref_prox_elem_nocoeff): a prebuilt library
+    from before that entry point serves every other comparison and none with them"""
+    return available() and hasattr(lib(), "ref_prox_elem_nocoeff")
+
+
 _lib = None
 
 
@@ -55,6 +61,8 @@ def lib():
         L.ref_problem_destroy.restype = None
         L.ref_prox_elem.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                     C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+        if hasattr(L, "ref_prox_elem_nocoeff"):          # absent from a library that an older driver was built into
+            L.ref_prox_elem_nocoeff.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]
         L.ref_project_epi_quad.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
         L.ref_csr2csc.argtypes = [C.c_int] * 4 + [C.c_void_p] * 6
         L.ref_linspace.argtypes = [C.c_double, C.c_double, C.c_int, C.c_void_p]
@@ -112,6 +120,14 @@ def prox_elem(op, fn, arg, tau_diag, tau, count, dim, interleaved, coeffs, inver
     fn_id = FN_ID[fn] if isinstance(fn, str) else fn
     _chk(lib().ref_prox_elem(_dt(arg.dtype), op, fn_id, _p(res), _p(arg), _p(tau_diag), float(tau),
                              int(invert_tau), count, dim, int(interleaved), ptrs, vals))
+    return res
+
+
+def prox_elem_nocoeff(op, arg, count, dim, interleaved):
+    """op: "ind_sum" (ElemOperationIndSum) or "ind_simplex" (ElemOperationIndSimplex), the functors without coefficients"""
+    arg = np.ascontiguousarray(arg)
+    res = np.zeros_like(arg)
+    _chk(lib().ref_prox_elem_nocoeff(_dt(arg.dtype), {"ind_sum": 2, "ind_simplex": 3}[op], _p(res), _p(arg), count, dim, int(interleaved)))
     return res
 
 

@@ -33,6 +33,13 @@ using std::abs; using std::max; using std::min;
 #include "prost/linop/linearoperator.hpp"
 #include "prost/problem.hpp"
 #include "prost/prox/elemop/elem_operation_1d.hpp"
+// the two functors without coefficients are declared __device__ only; their text is compiled as it stands, for the host as well
+#pragma push_macro("__device__")
+#undef __device__
+#define __device__ __attribute__((host)) __attribute__((device))
+#include "prost/prox/elemop/elem_operation_ind_simplex.hpp"
+#include "prost/prox/elemop/elem_operation_ind_sum.hpp"
+#pragma pop_macro("__device__")
 #include "prost/prox/elemop/elem_operation_norm2.hpp"
 #include "prost/prox/elemop/function_1d.hpp"
 #include "prost/prox/helper.hpp"
@@ -56,10 +63,15 @@ static void run_elem(T* d_res, const T* d_arg, const T* d_tau, T tau, bool inver
     Vector<T> res(count, dim, interleaved, tx, d_res);
     const Vector<const T> arg(count, dim, interleaved, tx, d_arg);
     const Vector<const T> tau_diag(count, dim, interleaved, tx, d_tau);
-    T coeffs_local[OP::kCoeffsCount];
+    T coeffs_local[OP::kCoeffsCount ? OP::kCoeffsCount : 1];
     for (size_t i = 0; i < OP::kCoeffsCount; i++) coeffs_local[i] = cptr[i] == nullptr ? cval[i] : cptr[i][tx];
-    OP op(coeffs_local, dim, sh_mem);
-    op(res, arg, tau_diag, tau, invert_tau);
+    if constexpr (OP::kCoeffsCount == 0) {          // ElemOperationIndSum / IndSimplex: no coefficients, constructor (dim, shared_mem)
+      OP op(dim, sh_mem);
+      op(res, arg, tau_diag, tau, invert_tau);
+    } else {
+      OP op(coeffs_local, dim, sh_mem);
+      op(res, arg, tau_diag, tau, invert_tau);
+    }
   }
 }
 
@@ -213,6 +225,21 @@ int ref_prox_elem(int dtype, int op, int fn, void* res, const void* arg, const v
     const double* cp[7]; double cv[7];
     for (int i = 0; i < 7; i++) { cp[i] = (const double*)(coeff_ptr ? coeff_ptr[i] : nullptr); cv[i] = coeff_val[i]; }
     elem_any<double>(op, fn, (double*)res, (const double*)arg, (const double*)tau_diag, tau, invert, count, dim, interleaved, cp, cv);
+  }
+  REF_CATCH
+}
+
+// ElemOperationIndSum (op 2) / ElemOperationIndSimplex (op 3) through the same host loop: no coefficients, the step is not read
+int ref_prox_elem_nocoeff(int dtype, int op, void* res, const void* arg, size_t count, size_t dim, int interleaved) {
+  REF_TRY
+  if (op != 2 && op != 3) throw Exception("bad operation id");
+  if (op == 3 && dim > MAX_DIM) throw Exception("ind_simplex: dim exceeds MAX_DIM");
+  if (dtype == 0) {
+    if (op == 2) run_elem<float, ElemOperationIndSum<float>>((float*)res, (const float*)arg, (const float*)arg, 1.f, false, count, dim, interleaved, nullptr, nullptr);
+    else run_elem<float, ElemOperationIndSimplex<float>>((float*)res, (const float*)arg, (const float*)arg, 1.f, false, count, dim, interleaved, nullptr, nullptr);
+  } else {
+    if (op == 2) run_elem<double, ElemOperationIndSum<double>>((double*)res, (const double*)arg, (const double*)arg, 1., false, count, dim, interleaved, nullptr, nullptr);
+    else run_elem<double, ElemOperationIndSimplex<double>>((double*)res, (const double*)arg, (const double*)arg, 1., false, count, dim, interleaved, nullptr, nullptr);
   }
   REF_CATCH
 }

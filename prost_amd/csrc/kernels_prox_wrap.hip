@@ -200,7 +200,7 @@ __global__ void __launch_bounds__(kBlock) elem_ind_simplex_kernel(T* __restrict_
     if (!bget) tmax = (T)(((double)(T)(tmpsum + a[(dim - 1) * count]) - 1.0) / (double)(T)dim);
     for (size_t i = 0; i < dim; i++) {
       const T v = arg[base + i * stride] - tmax;
-      res[base + i * stride] = v > (T)0 ? v : (T)0;            // max(val - tmax, 0): first argument wins on NaN
+      res[base + i * stride] = v < (T)0 ? (T)0 : v;            // std::max(val - tmax, 0): a NaN stays a NaN, as in the oracle and the host build of the functor
     }
   }
 }

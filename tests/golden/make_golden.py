@@ -170,11 +170,28 @@ def edges():
     np.savez_compressed(os.path.join(OUT, "elementwise_edges.npz"), **out)
 
 
+def wrap_edges():
+    """the answers of the reference's ElemOperationIndSimplex and ElemOperationIndSum on the directed operands of tests/prox_wrap_cases.py
+    (ties, sorted input, vertices, NaN, infinity; dims either side of the Shell-sort gaps), compared by tests/test_prox_wrap_edges.py:
+    one digest per case (answer_digest, 32 bytes)"""
+    sys.path.insert(0, os.path.dirname(OUT))
+    import prox_wrap_cases as W
+    import test_oracle_pinning as t
+    names, digests = [], []
+    for dt in W.DTYPES:
+        for name, c in W.fixture_cases(dt):
+            r = ref.prox_elem_nocoeff({"simplex": "ind_simplex", "elem_sum": "ind_sum"}[c.kind], c.arg, c.count, c.dim, c.interleaved)
+            names.append(name)
+            digests.append(bytes.fromhex(t.answer_digest(r)))
+    out = {"digest_keys": np.array(names, dtype="S"), "digests": np.frombuffer(b"".join(digests), dtype=np.uint8).reshape(len(names), 32)}
+    np.savez_compressed(os.path.join(OUT, "prox_wrap_edges.npz"), **out)
+
+
 if __name__ == "__main__":
     assert ref.available() or ref.build(), "oracle/_ref is not built and /root/reference is absent"
-    which = sys.argv[1:] or ["elementwise", "pdhg", "pdhg64", "misc", "live", "edges"]
+    which = sys.argv[1:] or ["elementwise", "pdhg", "pdhg64", "misc", "live", "edges", "wrap_edges"]
     for name in which:
-        {"elementwise": elementwise, "pdhg": pdhg, "pdhg64": pdhg64, "misc": misc, "live": live, "edges": edges}[name]()
+        {"elementwise": elementwise, "pdhg": pdhg, "pdhg64": pdhg64, "misc": misc, "live": live, "edges": edges, "wrap_edges": wrap_edges}[name]()
     for fn in sorted(os.listdir(OUT)):
         if fn.endswith(".npz"):
             print(fn, os.path.getsize(os.path.join(OUT, fn)) // 1024, "KiB")

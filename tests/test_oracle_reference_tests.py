@@ -7,6 +7,7 @@ import scipy.sparse as sp
 
 import oracle
 import prost_amd as prost
+from prox_wrap_cases import projsplx as _projsplx
 from reference_matrices import label_first_perm, spdiags_const, spmat_gradient2d, spmat_gradient3d
 
 DTYPES = [np.float32, np.float64]
@@ -313,13 +314,6 @@ def test_prox_ind_halfspace_and_soc(dtype):
     assert (np.sqrt((s[:, :-1] ** 2).sum(axis=1)) <= s[:, -1] + 1e-4).all()
     with pytest.raises(oracle.OracleError, match="Only alpha = 1"):
         oracle.eval_prox(prost.function.sum_ind_soc(dim, False, 2), W.reshape(-1, order="F"), 1, np.ones(count * dim), dtype)
-
-
-def _projsplx(y):
-    u = np.sort(y)[::-1]
-    css = np.cumsum(u)
-    rho = np.nonzero(u * np.arange(1, y.size + 1) > (css - 1))[0][-1]
-    return np.maximum(y - (css[rho] - 1) / (rho + 1), 0)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
